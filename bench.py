@@ -18,14 +18,23 @@ The reference publishes no KV/s; its end-to-end input throughput is
 0.85 GB/s aggregate on 20 GK104 GPUs (50 GB in 59.0 s), so
 `vs_baseline` compares our aggregate input GB/s with that number.
 
-The same invocation also runs the BASELINE headline's second workload,
-PageRank on RMAT-2^26 (edge factor 16, 20 iterations, strong scaling: the
-same graph for every N), and reports it in extra keys: pagerank_kvps (edge
-contributions per second over the timed iterations), pagerank_ms (one
-20-iteration run), pagerank_setup_ms (R-MAT generation + aggregate to the
-source owner + plan build) and pagerank_kvps_incl_setup.
+A plain run does only what that figure needs: set up, warm up, time the K
+steps, write the last step's outputs if --dump-outputs DIR is given, print
+the result line. Everything else is behind --full (off by default):
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload invertedindex|pagerank|wordfreq|trifind|intcount]
+With --full the same invocation also runs the BASELINE headline's second
+workload, PageRank on RMAT-2^26 (edge factor 16, 20 iterations, strong
+scaling: the same graph for every N), and reports it in extra keys:
+pagerank_kvps (edge contributions per second over the timed iterations),
+pagerank_ms (one 20-iteration run), pagerank_setup_ms (R-MAT generation +
+aggregate to the source owner + plan build) and pagerank_kvps_incl_setup;
+the other BASELINE configs (tri_find, wordfreq, the jobs with their file
+I/O, the multi-GPU plans on a forced one-rank RCCL communicator), the
+headline job again without the cross-job prefetch and once more per stage,
+the RCCL communicator check, and the full record in --detail-out.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                    [--workload invertedindex|pagerank|wordfreq|trifind|intcount|kmeans]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `--gpus N` without torchrun spawns the N ranks itself (one process per GPU,
@@ -69,6 +78,39 @@ def _sync(comm):
         torch.cuda.synchronize()
 
 
+DUMP_TEXT_BYTES = 8 << 20  # index text bytes dumped over all ranks (x4 as float32: the whole dump stays under 64 MB)
+DUMP_BLOCK = 4096
+
+
+def dump_inverted_index(comm, outdir, nurl, app):
+    """--dump-outputs: what the last timed job handed its caller, as .npy
+    files (rank 0: <name>.npy, rank r > 0: <name>_rank<r>.npy):
+      counts                 float64 [KV pairs emitted (all ranks), unique URLs of this rank, bytes of index text]
+      output_byte_histogram  float64 [256], how often each byte value occurs in this rank's index text
+      output_text            float32, the index text itself ("url\\tfile ...\\n" lines, one value per byte); a
+                             text longer than this rank's share of DUMP_TEXT_BYTES is sampled in whole 4 KiB
+                             blocks, chosen by a generator seeded with 0 from the text's length alone, in order
+    The inputs depend on the arguments only (seeded generators), so two builds
+    run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    app.output_ready()
+    text = app.output.cpu().numpy() if app.output is not None else np.zeros(0, dtype=np.uint8)
+    n = int(text.size)
+    budget = max(DUMP_BLOCK, DUMP_TEXT_BYTES // comm.size)
+    if n > budget:
+        nblk = -(-n // DUMP_BLOCK)
+        pick = np.sort(np.random.default_rng(0).choice(nblk, size=budget // DUMP_BLOCK, replace=False))
+        text_out = np.concatenate([text[b * DUMP_BLOCK:(b + 1) * DUMP_BLOCK] for b in pick])
+    else:
+        text_out = text
+    sfx = "" if comm.rank == 0 else f"_rank{comm.rank}"
+    np.save(os.path.join(outdir, f"counts{sfx}.npy"), np.array([nurl, app.nunique, n], dtype=np.float64))
+    np.save(os.path.join(outdir, f"output_byte_histogram{sfx}.npy"),
+            np.bincount(text, minlength=256).astype(np.float64))
+    np.save(os.path.join(outdir, f"output_text{sfx}.npy"), text_out.astype(np.float32))
+
+
 def bench_inverted_index(comm, args):
     from gpu_mapreduce_amd import MapReduce
     from gpu_mapreduce_amd.models.inverted_index import InvertedIndex
@@ -109,21 +151,27 @@ def bench_inverted_index(comm, args):
     _sync(comm)
     dt = (time.perf_counter() - t0) / args.steps
     dt = comm.allreduce(dt, "max", dtype=torch.float64)
-    # the same jobs strictly one after another (no cross-job prefetch), for reference
-    _sync(comm)
-    t1 = time.perf_counter()
-    steps(args.steps, False)
-    _sync(comm)
-    dt_serial = comm.allreduce((time.perf_counter() - t1) / args.steps, "max", dtype=torch.float64)
+    if args.dump_outputs:  # before any later job reuses the last step's pinned output slot
+        dump_inverted_index(comm, args.dump_outputs, nurl, app)
     total_in = comm.allreduce(in_bytes, "sum")
-    phases = {}
-    if args.phases:  # separate, device-synced run for the stage breakdown (not the timed steps)
-        mr = MapReduce(comm)
-        InvertedIndex(mr, files).run(phases)
-        phases = {k: round(v * 1e3, 3) for k, v in phases.items()}
+    more = {}
+    if args.full:
+        # the same jobs strictly one after another (no cross-job prefetch), for reference
+        _sync(comm)
+        t1 = time.perf_counter()
+        steps(args.steps, False)
+        _sync(comm)
+        dt_serial = comm.allreduce((time.perf_counter() - t1) / args.steps, "max", dtype=torch.float64)
+        phases = {}
+        if args.phases:  # separate, device-synced run for the stage breakdown (not the timed steps)
+            mr = MapReduce(comm)
+            InvertedIndex(mr, files).run(phases)
+            phases = {k: round(v * 1e3, 3) for k, v in phases.items()}
+        more = {"ms_per_step_no_prefetch": dt_serial * 1e3, "stage_ms": phases}
     value = nurl / dt
     gbps = total_in / dt / 1e9
     return {
+        **more,
         "metric": "KV-pairs/sec (whole node), InvertedIndex end-to-end",
         "value": value,
         "unit": "KV/s",
@@ -137,10 +185,8 @@ def bench_inverted_index(comm, args):
                       "as a pipeline: job s copies job s+1's first part file behind its own last one (the link does "
                       "not idle during job s's tail); the last timed job prefetches nothing and the first timed job "
                       "copies all its files inside the window",
-        "ms_per_step_no_prefetch": dt_serial * 1e3,
         "kv_pairs_per_step": nurl,
         "unique_urls": app.nunique,
-        "stage_ms": phases,
         "step_ms_rank0": step_ms,
         "config": {"model": "InvertedIndex", "global_batch": total_in, "seq_len": args.file_bytes,
                    "parallelism": f"dp{comm.size}", "bytes_per_gpu": per_gpu,
@@ -687,7 +733,7 @@ def main():
     ap.add_argument("--file-bytes", type=int, default=128 << 20)
     ap.add_argument("--link-gap", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--phases", type=int, default=1, help="also report a per-stage breakdown (extra run)")
+    ap.add_argument("--phases", type=int, default=1, help="with --full: also report a per-stage breakdown (extra run)")
     ap.add_argument("--scale", type=int, default=None, help="RMAT scale (pagerank 26, trifind 24)")
     ap.add_argument("--edgefactor", type=int, default=16, help="RMAT edges per vertex")
     ap.add_argument("--intcount-bytes", type=int, default=128 << 20, help="intcount: raw int32 bytes per GPU")
@@ -721,7 +767,15 @@ def main():
                     help="timed steps of the headline job with part-file reads and output write (0 = skip)")
     ap.add_argument("--detail-out", default="gpurun_out/bench_detail.json",
                     help="rank 0 writes the full record (stage arrays, notes) here; '' = don't")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the other BASELINE workloads, the file-I/O "
+                         "and no-prefetch variants, the stage breakdown, the RCCL communicator check, the detail file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(invertedindex: see dump_inverted_index)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "invertedindex":
+        ap.error("--dump-outputs is implemented for --workload invertedindex")
     if args.scale is None:
         args.scale = 24 if args.workload == "trifind" else 26
 
@@ -771,7 +825,7 @@ def main():
         from gpu_mapreduce_amd.models.wordfreq import bench_wordfreq
         res = bench_wordfreq(comm, args)
     # before the extras: a failing extra poisons (aborts) the communicator
-    rrec = rccl_record(comm)
+    rrec = rccl_record(comm) if args.full else {"engine_transport": comm.native.transport}
     peaks = {}
 
     def mark(part):
@@ -782,7 +836,8 @@ def main():
             peaks[part] = hbm_pool.stats(dev)["peak"]
             hbm_pool.reset_peak(dev)
     mark(args.workload)
-    if args.workload == "invertedindex" and args.pagerank_scale > 0:
+    extras = args.full and args.workload == "invertedindex"
+    if extras and args.pagerank_scale > 0:
         # the headline line is printed even if the PageRank extra fails (its
         # peers fail fast through the engine's peer monitor); the error is
         # reported in the record instead of the PageRank keys
@@ -792,7 +847,7 @@ def main():
             res["pagerank_error"] = f"{type(e).__name__}: {e}"[:500]
             print(f"bench.py rank {comm.rank}: PageRank extra failed: {e}", file=sys.stderr, flush=True)
         mark("pagerank")
-    if args.workload == "invertedindex" and args.file_io_steps > 0:
+    if extras and args.file_io_steps > 0:
         # the headline job again with its file reads and output write (the
         # reference's end-to-end scope), failure-isolated
         try:
@@ -803,7 +858,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             res["with_file_io"] = {"error": f"{type(e).__name__}: {e}"[:500]}
         mark("with_file_io")
-    if args.workload == "invertedindex":
+    if extras:
         # BASELINE configs 5 and 3 in the same driver-measured record
         if args.trifind_scale > 0:
             from gpu_mapreduce_amd.models.triangles import bench_trifind
@@ -882,7 +937,7 @@ def main():
         # the whole record (per-stage arrays, notes, configs) goes to a side
         # file; the printed line carries every BASELINE-config number in a few
         # kB so that all of it is inside the driver's stdout tail
-        detail = args.detail_out
+        detail = args.detail_out if args.full else ""  # a plain run writes no file but --dump-outputs'
         if detail:
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)

@@ -16,11 +16,11 @@ ARGS = ["--bytes-per-gpu", "4e6", "--file-bytes", "1000000", "--steps", "1", "--
 
 
 def _bench(n, tmp, extra=()):
-    """the printed line merged over the detail file (the full record)"""
+    """the printed line of a --full run merged over the detail file (the full record)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HIP_VISIBLE_DEVICES"] = ""
     detail = os.path.join(str(tmp), f"detail_{n}.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *ARGS, *extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *ARGS, *extra, "--full",
                         "--detail-out", detail], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -85,6 +85,52 @@ def test_bench_rejects_world_size_mismatch():
     assert r.returncode == 2 and "WORLD_SIZE=2" in r.stderr
 
 
+def _plain(tmp, tag, steps):
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["HIP_VISIBLE_DEVICES"] = ""
+    dump = os.path.join(str(tmp), tag)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--bytes-per-gpu", "4e6",
+                        "--file-bytes", "1000000", "--steps", str(steps), "--warmup", "1", "--dump-outputs", dump],
+                       cwd=str(tmp), env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0]), dump
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """without --full: the headline keys only, --steps timed steps, no detail
+    file; --dump-outputs writes the last timed job's outputs, the same from
+    run to run and whatever the number of steps (the inputs are seeded)"""
+    import numpy as np
+    a, da = _plain(tmp_path, "a", 3)
+    b, db = _plain(tmp_path, "b", 1)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in a, k
+    assert a["steps"] == 3 and b["steps"] == 1 and a["ms_per_step"] > 0
+    assert a["unit"] == "KV/s" and a["higher_is_better"] is True
+    assert a["value"] == pytest.approx(a["kv_pairs_per_step"] / (a["ms_per_step"] * 1e-3))
+    moved = [k for k in a if k.startswith(("pagerank", "trifind", "wordfreq", "with_file_io", "rccl", "ii_stage"))
+             or k in ("ms_per_step_no_prefetch", "detail_file")]
+    assert not moved, moved
+    assert sorted(os.listdir(tmp_path)) == ["a", "b"]  # nothing but the dumps was written
+    names = sorted(os.listdir(da))
+    assert names == ["counts.npy", "output_byte_histogram.npy", "output_text.npy"] == sorted(os.listdir(db))
+    total = 0
+    for nm in names:
+        x, y = np.load(os.path.join(da, nm)), np.load(os.path.join(db, nm))
+        assert x.dtype in (np.float32, np.float64) and x.size > 0
+        np.testing.assert_array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64e6
+    counts = np.load(os.path.join(da, "counts.npy"))
+    text = np.load(os.path.join(da, "output_text.npy"))
+    assert counts[0] == a["kv_pairs_per_step"] and counts[1] == a["unique_urls"] and counts[2] == text.size
+    assert np.load(os.path.join(da, "output_byte_histogram.npy")).sum() == counts[2]
+    lines = bytes(text.astype(np.uint8)).splitlines()
+    assert len(lines) == a["unique_urls"] and all(b"\t" in l for l in lines)
+
+
 @pytest.mark.gpu
 def test_bench_two_ranks_on_one_gpu():
     """bench.py --gpus 2 on a 1-GPU box: both ranks share cuda:0 (RCCL refuses
@@ -95,7 +141,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MRH_DIST_BACKEND="gloo", MRH_TRANSPORT="pg", MRH_NUMA_BIND="0")
     args = ["--bytes-per-gpu", "32e6", "--file-bytes", "8000000", "--steps", "2", "--warmup", "1", "--phases", "0",
-            "--pagerank-scale", "16", "--pagerank-steps", "1"]
+            "--pagerank-scale", "16", "--pagerank-steps", "1", "--full"]
     out = {}
     for n in (1, 2):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args], cwd=ROOT,

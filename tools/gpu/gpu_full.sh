@@ -16,7 +16,7 @@ step() {  # name seconds cmd...
 }
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread -p no:cacheprovider || exit $?
 step smoke 200 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-step bench_$T 300 python bench.py || exit $?
+step bench_$T 300 python bench.py --full || exit $?
 step pr_prof_$T 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_pr_$T -o p -- python3 bench.py --workload pagerank --steps 1 --warmup 0 || exit $?
 step pr_pmc_$T 120 timeout -s KILL 110 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d gpurun_out/pmc_pr_$T -o p -- python3 bench.py --workload pagerank --steps 1 --warmup 0 --iters 3 || exit $?
 exit 0
