@@ -1073,6 +1073,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return d;
   });
   m.def("spool_writer_reset_peak", &mrh::spool_writer_reset_peak);
+  // one step of the convert pipeline for tests (ooc.h upload_spool): the
+  // pieces go into a fresh spool with unlimited budgets on the current
+  // stream, are uploaded on a pool side stream (the CPU engine has none), and
+  // the current stream takes the result over as the pipeline's loop does
+  m.def("spool_upload", [](const std::vector<KV>& pieces, const std::string& device) {
+    const at::Device dev(device);
+    Spool sp(dev, SpoolConfig());
+    for (const KV& p : pieces) sp.add(p);
+    c10::optional<c10::hip::HIPStream> side;
+    if (dev.is_cuda()) side = c10::hip::getStreamFromPool(false, dev.index());
+    Upload up = upload_spool(sp, dev, side);
+    if (dev.is_cuda()) {
+      const hipStream_t cs = at::hip::getCurrentHIPStream().stream();
+      up.done.wait_on(cs);
+      use_on(up.kv, cs);
+    }
+    if (!up.hold.empty()) up.done.sync();  // pinned sources are dropped on return
+    return up.kv;
+  });
   // world size 1 runs the local transport (no communicator); this builds a
   // one-rank RCCL communicator on `device` and returns what RCCL reports
   m.def("rccl_self_probe", [](int device) {

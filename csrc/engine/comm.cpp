@@ -23,6 +23,7 @@
 
 #include "guard.h"
 #include "storepg.h"
+#include "streams.h"
 
 namespace mrh {
 
@@ -223,22 +224,14 @@ void Comm::poison(const std::string& why) const {
 
 void Comm::host_wait() const {
   if (!dev_.is_cuda()) return;
-  hipEvent_t ev;
-  if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-    throw std::runtime_error("mrhip: hipEventCreate failed");
-  struct Drop {
-    hipEvent_t e;
-    ~Drop() { (void)hipEventDestroy(e); }  // destructor: cannot throw
-  } drop{ev};
-  if (hipEventRecord(ev, cur(dev_)) != hipSuccess) throw std::runtime_error("mrhip: hipEventRecord failed");
+  Event ev;
+  ev.record(cur(dev_), "mrhip: hipEventRecord failed");
   // the deadline replaces the watchdog of a c10d RCCL group: a collective
   // whose peer never posts its half cannot block this rank forever
   const bool bounded = distributed() && size_ > 1;
   const double t0 = bounded ? wtime() : 0.0, limit = guard::comm_timeout_seconds();
   for (int spin = 0;; ++spin) {
-    const hipError_t q = hipEventQuery(ev);
-    if (q == hipSuccess) return;
-    if (q != hipErrorNotReady) throw std::runtime_error(std::string("mrhip: device error: ") + hipGetErrorString(q));
+    if (ev.done("mrhip: device error")) return;
     if (bounded && (spin & 255) == 0 && wtime() - t0 > limit)
       fail_now("mrhip: device work did not complete within MRH_COMM_TIMEOUT=" + std::to_string((int)limit) +
                " s (a collective whose peers never joined?)");

@@ -63,11 +63,6 @@ KV kv_to(const KV& kv, at::Device dev);
 KV concat(const std::vector<KV>& parts, at::Device dev, bool pin = false);
 // KMVs one after the other (keys, values, rebased segments) on dev
 KMV kmv_concat(const std::vector<KMV>& parts, at::Device dev, bool pin = false);
-// the parts copied host -> device straight into one device KV (no host
-// concatenation; fixed widths and offsets alike)
-// (hold set: pinned sources are copied by hipMemcpyAsync on the current
-// stream and appended to *hold, which the caller keeps until the stream passed
-// the copies)
 // device scalars read on the host with one synchronisation of stream s
 // (pinned staging; no ATen kernels): {device src, host dst, bytes}
 struct SmallRead {
@@ -89,6 +84,12 @@ UploadTimes& upload_times();
 // with a multi-threaded memcpy (never HIP's on-the-fly pinning of pageable memory)
 // (non_blocking: a pinned source may still be read by the copy when this returns)
 at::Tensor to_device(const at::Tensor& t, at::Device dev, bool non_blocking = false);
+// the parts copied straight into one device KV on the current stream (no host
+// concatenation; fixed widths and offsets alike). Stream rules (streams.h):
+// device parts must be readable on the current stream and safe to free once
+// this returns — what Spool::take() hands out is; with `hold` set, pinned
+// parts are copied asynchronously and appended to *hold, which the caller
+// keeps until the stream has passed the copies.
 KV concat_upload(const std::vector<KV>& parts, at::Device dev, std::vector<at::Tensor>* hold = nullptr);
 KV to_var_keys(const KV& kv);
 KV to_var_values(const KV& kv);

@@ -33,7 +33,6 @@
 // (Spool::add with a stream) while chunk k+1 is partitioned.
 #include <ATen/ATen.h>
 #include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPCachingAllocator.h>
 #include <c10/hip/HIPGuard.h>
 
 #include <algorithm>
@@ -52,6 +51,7 @@
 #include "comm.h"
 #include "ooc.h"
 #include "spool.h"
+#include "streams.h"
 #include "xfer.h"
 
 namespace mrh {
@@ -209,18 +209,13 @@ std::vector<std::pair<int64_t, int64_t>> chunks(const KV& kv, const HostOff& h, 
 // does not recycle them while `use` still reads them
 KV kv_to_async(const KV& kv, at::Device dev, const c10::hip::HIPStream& side, const c10::hip::HIPStream& use) {
   c10::hip::HIPStreamGuard g(side);
-  auto one = [&](const at::Tensor& t) {
-    if (!t.defined()) return t;
-    note_xfer(t, dev);
-    at::Tensor d = to_device(t, dev, /*non_blocking=*/true);  // pageable (spool file) pieces: staging ring
-    if (d.is_cuda()) c10::hip::HIPCachingAllocator::recordStream(d.storage().data_ptr(), use);
-    return d;
-  };
   KV o = kv;
-  o.kdata = one(kv.kdata);
-  o.vdata = one(kv.vdata);
-  o.koff = one(kv.koff);
-  o.voff = one(kv.voff);
+  for (at::Tensor* t : {&o.kdata, &o.vdata, &o.koff, &o.voff}) {
+    if (!t->defined()) continue;
+    note_xfer(*t, dev);
+    *t = to_device(*t, dev, /*non_blocking=*/true);  // pageable (spool file) pieces: staging ring
+  }
+  use_on(o, use.stream());
   return o;
 }
 
@@ -275,31 +270,19 @@ std::vector<Spool> spool(const std::vector<KV>& kvs, int64_t cap, at::Device dev
     if (!cuda || !kv.device().is_cpu()) return kv_to(slice, dev);
     return kv_to_async(slice, dev, *side, *main);
   };
-  std::vector<hipEvent_t> ready(2, nullptr);
-  if (cuda)
-    for (auto& e : ready)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) throw std::runtime_error("ooc: event");
-  struct Ev {
-    std::vector<hipEvent_t>* v;
-    ~Ev() {
-      for (auto e : *v)
-        if (e) (void)hipEventDestroy(e);
-    }
-  } ev_guard{&ready};
+  Event ready[2];  // chunk i is on the device (recorded on the side stream)
   PhaseClock clk("spool");
   KV next;
   if (!ch.empty()) {
     next = load(0);
-    if (cuda && hipEventRecord(ready[0], side->stream()) != hipSuccess) throw std::runtime_error("ooc: event");
+    if (cuda) ready[0].record(side->stream(), "ooc: event");
   }
   for (size_t i = 0; i < ch.size(); ++i) {
     KV c = next;
-    if (cuda && hipStreamWaitEvent(main->stream(), ready[i % 2], 0) != hipSuccess)
-      throw std::runtime_error("ooc: stream wait");
+    if (cuda) ready[i % 2].wait_on(main->stream(), "ooc: stream wait");
     if (i + 1 < ch.size()) {  // chunk i+1 on the PCIe link while chunk i partitions
       next = load(i + 1);
-      if (cuda && hipEventRecord(ready[(i + 1) % 2], side->stream()) != hipSuccess)
-        throw std::runtime_error("ooc: event");
+      if (cuda) ready[(i + 1) % 2].record(side->stream(), "ooc: event");
     }
     clk("load");
     at::Tensor dest = dest_of(c);
@@ -329,7 +312,7 @@ std::vector<Spool> spool(const std::vector<KV>& kvs, int64_t cap, at::Device dev
       const int64_t s0 = s;
       if (s0 < B.kv.n) {
         KV hk;
-        const std::shared_ptr<DrainEvent> ev =
+        const std::shared_ptr<Event> ev =
             drain_to_pinned(s0 ? kv_slice(B.kv, s0, B.kv.n, nullptr, nullptr) : B.kv, drain->stream(), &hk);
         clk("drain issue");
         for (int d = dk; d < M; ++d) {
@@ -604,6 +587,19 @@ void ooc_convert_big(std::vector<KV> pieces, const OocEnv& env, at::Device dev, 
 
 }  // namespace
 
+Upload upload_spool(Spool& sp, at::Device dev, const c10::optional<c10::hip::HIPStream>& side,
+                    const std::function<void(const char*)>& mark) {
+  Upload up;
+  c10::hip::OptionalHIPStreamGuard g;
+  if (side) g.reset_stream(*side);
+  const std::vector<KV> pieces = sp.take();  // (hands its HBM-tier pieces to `side`)
+  if (mark) mark("take (drains, file writes)");
+  up.kv = concat_upload(pieces, dev, side ? &up.hold : nullptr);
+  if (mark) mark("upload issue");
+  if (side) up.done.record(side->stream(), "ooc: upload failed");
+  return up;
+}
+
 std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env, at::Device dev, OocStats* st) {
   const int64_t budget = env.hbm;
   int64_t bytes = 0;
@@ -635,7 +631,7 @@ std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env
     ups = c10::hip::getStreamFromPool(false, dev.index());
     dns = c10::hip::getStreamFromPool(false, dev.index());
   }
-  std::vector<std::shared_ptr<DrainEvent>> drains;
+  std::vector<Event> drains;
   // in_file: a hot key whose values one_key_kmv already put in a file
   auto keep = [&](KMV&& m, bool in_file) {
     const int64_t b = m.nbytes();
@@ -647,16 +643,11 @@ std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env
         out.push_back(m);
       } else if (pipe) {
         const hipStream_t c = dns->stream();
-        fence_after_current(c);
+        order_after(c);
         KMV h = m;
-        h.keys.kdata = drain_tensor(m.keys.kdata, c);
-        h.keys.vdata = drain_tensor(m.keys.vdata, c);
-        h.keys.koff = drain_tensor(m.keys.koff, c);
-        h.keys.voff = drain_tensor(m.keys.voff, c);
-        h.vdata = drain_tensor(m.vdata, c);
-        h.voff = drain_tensor(m.voff, c);
-        h.seg = drain_tensor(m.seg, c);
-        drains.push_back(record_event(c));
+        for (at::Tensor* t : {&h.keys.kdata, &h.keys.vdata, &h.keys.koff, &h.keys.voff, &h.vdata, &h.voff, &h.seg})
+          *t = drain_tensor(*t, c);
+        drains.emplace_back().record(c, "ooc: result drain failed");
         out.push_back(h);
       } else {
         out.push_back(kmv_host(m));
@@ -671,31 +662,15 @@ std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env
     }
   };
   auto fits = [&](int d) { return !parts[d].empty() && parts[d].bytes() * 4 <= budget; };
-  // partition d's pieces straight into one device KV (no host concat); on
-  // the upload stream when pipelined (the pool orders the new blocks there)
-  // pinned pieces of an upload, held until its event passed
-  std::vector<std::pair<std::shared_ptr<DrainEvent>, std::vector<at::Tensor>>> held;
-  auto upload = [&](int d, std::shared_ptr<DrainEvent>* ev) {
-    if (!pipe) return concat_upload(parts[d].take(), dev);
-    for (size_t i = 0; i < held.size();)  // release the sources of finished uploads
-      if (hipEventQuery(held[i].first->e) == hipSuccess) held.erase(held.begin() + (long)i);
-      else ++i;
-    KV p;
-    std::vector<at::Tensor> hold;
-    {
-      c10::hip::HIPStreamGuard g(*ups);
-      std::vector<KV> pieces = parts[d].take();
-      clk("take (drains, file writes)");
-      p = concat_upload(pieces, dev, &hold);
-      clk("upload issue");
-    }
-    *ev = record_event(ups->stream());
-    held.emplace_back(*ev, std::move(hold));
-    return p;
+  // uploads whose pinned sources are held until their event passed
+  std::vector<Upload> held;
+  auto upload = [&](int d) {
+    held.erase(std::remove_if(held.begin(), held.end(), [](const Upload& u) { return u.done.done("ooc: upload failed"); }),
+               held.end());
+    return upload_spool(parts[d], dev, ups, [&](const char* what) { clk(what); });
   };
   int pre_d = -1;
-  KV pre;
-  std::shared_ptr<DrainEvent> pre_ev;
+  Upload pre;
   for (int d = 0; d < M; ++d) {
     // (a prefetched partition's spool is already empty: its pieces are in pre)
     if (pre_d != d && parts[d].empty()) continue;
@@ -703,28 +678,20 @@ std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env
       ooc_convert_big(parts[d].take(), env, dev, st, 1, keep);
       continue;
     }
-    KV p;
-    std::shared_ptr<DrainEvent> ev;
-    if (pre_d == d) {
-      p = std::move(pre);
-      ev = std::move(pre_ev);
-      pre = KV();
-      pre_d = -1;
-    } else {
-      p = upload(d, &ev);
-    }
-    if (ev) {  // the current stream reads what the upload stream wrote
+    Upload up = pre_d == d ? std::move(pre) : upload(d);
+    if (pre_d == d) pre_d = -1;
+    KV p = std::move(up.kv);
+    if (pipe) {  // the current stream reads what the upload stream wrote
       const hipStream_t cs = at::hip::getCurrentHIPStream().stream();
-      if (hipStreamWaitEvent(cs, ev->e, 0) != hipSuccess) throw std::runtime_error("ooc: upload wait");
-      for (const at::Tensor* t : {&p.kdata, &p.vdata, &p.koff, &p.voff})
-        if (t->defined() && t->is_cuda())
-          c10::hip::HIPCachingAllocator::recordStream(t->storage().data_ptr(), at::hip::getCurrentHIPStream());
+      up.done.wait_on(cs, "ooc: upload wait");
+      use_on(p, cs);
+      held.push_back(std::move(up));
     }
     clk("to device");
     int n = d + 1;
     while (n < M && parts[n].empty()) ++n;
     if (n < M && fits(n)) {  // (on the CPU too: the same bookkeeping, no streams)
-      pre = upload(n, &pre_ev);
+      pre = upload(n);
       pre_d = n;
     }
     clk("prefetch");
@@ -734,10 +701,8 @@ std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env
     keep(std::move(m), false);
     clk("result to host");
   }
-  for (const auto& e : drains)
-    if (hipEventSynchronize(e->e) != hipSuccess) throw std::runtime_error("ooc: result drain failed");
-  for (const auto& h : held)
-    if (hipEventSynchronize(h.first->e) != hipSuccess) throw std::runtime_error("ooc: upload failed");
+  for (const Event& e : drains) e.sync("ooc: result drain failed");
+  for (const Upload& u : held) u.done.sync("ooc: upload failed");
   clk("drain sync");
   if (out.empty()) out.push_back(kmv_concat_host(out, kv));  // an empty KMV of the KV's widths
   return out;

@@ -4,7 +4,10 @@
 #include <functional>
 #include <string>
 
+#include <c10/hip/HIPStream.h>
+
 #include "kv.h"
+#include "spool.h"
 
 namespace mrh {
 
@@ -40,6 +43,21 @@ KMV ooc_convert(const std::vector<KV>& kvs, const OocEnv& env, at::Device dev, O
 // object keeps them as its KMV's parts
 std::vector<KMV> ooc_convert_parts(const std::vector<KV>& kvs, const OocEnv& env, at::Device dev,
                                    OocStats* st = nullptr);
+// One partition's upload in the convert pipeline: the spool's pieces are taken
+// and copied straight into one device KV (concat_upload, no host concat) with
+// `side` as the current stream; `done` is then recorded on `side`. Whoever
+// reads `kv` on another stream makes it wait for `done` and marks kv with
+// use_on for it; `hold` (the pinned sources) is kept until `done` has passed
+// (streams.h, rule 3). Without `side` (the CPU engine, no pipeline) the copy
+// runs on the current stream and `done` stays unset: waiting for it is a no-op.
+// mark: phase names for MRH_OOC_TRACE.
+struct Upload {
+  KV kv;
+  Event done;
+  std::vector<at::Tensor> hold;
+};
+Upload upload_spool(Spool& sp, at::Device dev, const c10::optional<c10::hip::HIPStream>& side,
+                    const std::function<void(const char*)>& mark = nullptr);
 KV ooc_sort(const KV& kv, int flag, bool by_value, const OocEnv& env, at::Device dev, OocStats* st = nullptr);
 KV ooc_reduce_builtin(const KMV& kmv, const std::string& op, const std::string& dtype, const OocEnv& env,
                       at::Device dev, OocStats* st = nullptr);

@@ -47,6 +47,7 @@
 #include "comm.h"
 #include "guard.h"
 #include "kv.h"
+#include "streams.h"
 
 namespace mrh {
 
@@ -466,7 +467,9 @@ KV exchange(KV kv, const at::Tensor& dest_given, const Comm& comm, const Exchang
   // ---- 6. rounds
   const hipStream_t cs_ = s;
   at::Tensor stage[2];
-  hipEvent_t drained[2] = {nullptr, nullptr};
+  Event drained[2];  // staging buffer k%2 has been copied to the host
+  // the checked-HIP-call sites of the drains (MRH_FAULT=hip:<site>:<rank>)
+  auto site = [me](const char* name) { guard::hip_check(hipSuccess, name, me); };
   c10::optional<c10::hip::HIPStream> copy_stream;
   int64_t stage_bytes = 0;
   if (host_sink) {
@@ -479,7 +482,6 @@ KV exchange(KV kv, const at::Tensor& dest_given, const Comm& comm, const Exchang
     }
     for (auto& t : stage) t = at::empty({std::max<int64_t>(stage_bytes, 1)}, opt(dev, at::kByte));
     copy_stream = c10::hip::getStreamFromPool(false, dev.index());
-    for (auto& e : drained) guard::hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "drain_event", me);
   }
   // an exception out of the rounds (a failed drain, a peer failure) must not
   // unwind while drain copies still write into the output being freed
@@ -532,17 +534,17 @@ KV exchange(KV kv, const at::Tensor& dest_given, const Comm& comm, const Exchang
       continue;
     }
     // staging buffer k%2 is free once the drain of round k-2 finished
-    if (k >= 2) guard::hip_check(hipStreamWaitEvent(cs_, drained[k % 2], 0), "drain_wait", me);
-    hipEvent_t landed = nullptr;
-    if (comm.uses_rccl()) {
-      landed = comm.rccl()->sendrecv_async(xs, xr, cs_);
+    site("drain_wait");
+    drained[k % 2].wait_on(cs_, "mrhip: exchange drain_wait");  // (unset in rounds 0 and 1)
+    const hipStream_t cp = copy_stream->stream();
+    if (comm.uses_rccl()) {  // `landed` belongs to the communicator's ring
+      const hipEvent_t landed = comm.rccl()->sendrecv_async(xs, xr, cs_);
+      guard::hip_check(hipStreamWaitEvent(cp, landed, 0), "drain_wait", me);
     } else {
       comm.sendrecv(xs, xr);
-      guard::hip_check(hipEventCreateWithFlags(&landed, hipEventDisableTiming), "landed_event", me);
-      guard::hip_check(hipEventRecord(landed, cs_), "landed_event", me);
+      site("landed_event");
+      order_after(cp, cs_, "mrhip: exchange landed_event");
     }
-    const hipStream_t cp = copy_stream->stream();
-    guard::hip_check(hipStreamWaitEvent(cp, landed, 0), "drain_wait", me);
     for (const Drain& d : drains) {
       note_xfer_bytes(false, d.bytes);
       if (d.bytes)
@@ -550,13 +552,12 @@ KV exchange(KV kv, const at::Tensor& dest_given, const Comm& comm, const Exchang
                                         hipMemcpyDeviceToHost, cp),
                          "drain_copy", me);
     }
-    guard::hip_check(hipEventRecord(drained[k % 2], cp), "drain_event", me);
-    if (!comm.uses_rccl()) guard::hip_check(hipEventDestroy(landed), "landed_event", me);
+    site("drain_event");
+    drained[k % 2].record(cp, "mrhip: exchange drain_event");
   }
   if (host_sink) {
-    for (int k = std::max(0, R - 2); k < R; ++k) guard::hip_check(hipStreamWaitEvent(cs_, drained[k % 2], 0), "drain_wait", me);
+    for (const Event& e : drained) e.wait_on(cs_, "mrhip: exchange drain_wait");
     comm.host_wait();  // pinned host output complete before the host reads it
-    for (auto& e : drained) guard::hip_check(hipEventDestroy(e), "drain_event", me);
   }
 
   // ---- 7. offsets of variable columns

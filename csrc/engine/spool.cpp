@@ -4,7 +4,6 @@
 #include "spool.h"
 
 #include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPCachingAllocator.h>
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -27,6 +26,7 @@ namespace {
 
 at::TensorOptions opt(at::Device d, at::ScalarType t) { return at::TensorOptions().device(d).dtype(t); }
 [[noreturn]] void fail(const std::string& m) { throw std::runtime_error("mrhip spool: " + m); }
+constexpr const char* kDrainFailed = "mrhip spool: asynchronous drain failed";
 
 std::atomic<int64_t> g_files_live{0};
 std::atomic<int64_t> g_counter{0};
@@ -369,7 +369,7 @@ class DiskWriter {
     static DiskWriter* w = new DiskWriter();  // never destroyed: no join at exit
     return *w;
   }
-  std::future<KV> submit(KV piece, std::shared_ptr<DrainEvent> ev, std::string path) {
+  std::future<KV> submit(KV piece, std::shared_ptr<Event> ev, std::string path) {
     const int64_t b = std::max<int64_t>(1, piece.nbytes());
     auto job = std::make_unique<Job>();
     job->piece = std::move(piece);
@@ -408,7 +408,7 @@ class DiskWriter {
  private:
   struct Job {
     KV piece;
-    std::shared_ptr<DrainEvent> ev;
+    std::shared_ptr<Event> ev;
     std::string path;
     int64_t bytes = 0;
     std::promise<KV> done;
@@ -431,8 +431,7 @@ class DiskWriter {
         q_.pop_front();
       }
       try {
-        const hipError_t r = hipEventSynchronize(j->ev->e);
-        if (r != hipSuccess) fail(std::string("asynchronous drain failed: ") + hipGetErrorString(r));
+        j->ev->sync(kDrainFailed);
         KV out = kv_to_file({j->piece}, j->path);
         j->piece = KV();  // the pinned source goes back now, not when the spool is read
         j->ev.reset();
@@ -484,23 +483,19 @@ void Spool::sync() {
   }
   writing_.clear();
   if (err) std::rethrow_exception(err);
-  for (const auto& ev : pending_) {
-    const hipError_t r = hipEventSynchronize(ev->e);
-    if (r != hipSuccess) {
-      pending_.clear();
-      fail(std::string("asynchronous drain failed: ") + hipGetErrorString(r));
-    }
-  }
-  pending_.clear();
+  std::vector<std::shared_ptr<Event>> pending;
+  pending.swap(pending_);  // dropped on an error too
+  for (const auto& ev : pending) ev->sync(kDrainFailed);
 }
 
-void fence_after_current(hipStream_t copy) {
-  hipStream_t cs = at::hip::getCurrentHIPStream().stream();
-  hipEvent_t fence;
-  if (hipEventCreateWithFlags(&fence, hipEventDisableTiming) != hipSuccess || hipEventRecord(fence, cs) != hipSuccess ||
-      hipStreamWaitEvent(copy, fence, 0) != hipSuccess)
-    fail("drain fence failed");
-  (void)hipEventDestroy(fence);
+void Spool::ready() {
+  sync();
+  if (!hbm_written_) return;
+  const hipStream_t cs = at::hip::getCurrentHIPStream(dev_.index()).stream();
+  if (cs == hbm_stream_) return;
+  hbm_written_.wait_on(cs, "mrhip spool: HBM tier hand-off failed");
+  for (size_t i = 0; i < pieces_.size(); ++i)
+    if (tier_[i] == 0) use_on(pieces_[i], cs);
 }
 
 at::Tensor drain_tensor(const at::Tensor& t, hipStream_t copy) {
@@ -511,30 +506,21 @@ at::Tensor drain_tensor(const at::Tensor& t, hipStream_t copy) {
   const size_t nb = (size_t)src.numel() * src.element_size();
   if (nb && hipMemcpyAsync(o.data_ptr(), src.data_ptr(), nb, hipMemcpyDeviceToHost, copy) != hipSuccess)
     fail("asynchronous drain copy failed");
-  c10::hip::HIPCachingAllocator::recordStream(src.storage().data_ptr(),
-                                             c10::hip::getStreamFromExternal(copy, src.device().index()));
+  use_on(src, copy);  // the source may be freed before the copy ran
   return o;
 }
 
-std::shared_ptr<DrainEvent> record_event(hipStream_t s) {
-  auto ev = std::make_shared<DrainEvent>();
-  if (hipEventCreateWithFlags(&ev->e, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev->e, s) != hipSuccess)
-    fail("drain event failed");
-  return ev;
+std::shared_ptr<Event> drain_to_pinned(const KV& dev_kv, hipStream_t copy, KV* host_out) {
+  order_after(copy);
+  *host_out = dev_kv;
+  for (at::Tensor* t : {&host_out->kdata, &host_out->vdata, &host_out->koff, &host_out->voff})
+    *t = drain_tensor(*t, copy);
+  auto done = std::make_shared<Event>();
+  done->record(copy, "mrhip spool: drain event failed");
+  return done;
 }
 
-std::shared_ptr<DrainEvent> drain_to_pinned(const KV& dev_kv, hipStream_t copy, KV* host_out) {
-  fence_after_current(copy);
-  KV o = dev_kv;
-  o.kdata = drain_tensor(dev_kv.kdata, copy);
-  o.vdata = drain_tensor(dev_kv.vdata, copy);
-  o.koff = drain_tensor(dev_kv.koff, copy);
-  o.voff = drain_tensor(dev_kv.voff, copy);
-  *host_out = o;
-  return record_event(copy);
-}
-
-void Spool::add_drained(const KV& piece, const std::shared_ptr<DrainEvent>& ev) {
+void Spool::add_drained(const KV& piece, const std::shared_ptr<Event>& ev) {
   if (piece.n == 0) return;
   const int64_t b = piece.nbytes();
   SpoolBudget& B = *cfg_.budget;
@@ -549,7 +535,7 @@ void Spool::add_drained(const KV& piece, const std::shared_ptr<DrainEvent>& ev) 
   totals_piece();
 }
 
-void Spool::add_drained_to_disk(const KV& piece, const std::shared_ptr<DrainEvent>& ev) {
+void Spool::add_drained_to_disk(const KV& piece, const std::shared_ptr<Event>& ev) {
   if (piece.n == 0) return;
   const int64_t b = piece.nbytes();
   writing_.emplace_back(pieces_.size(), DiskWriter::get().submit(piece, ev, next_path()));
@@ -599,6 +585,12 @@ void Spool::add(const KV& piece, hipStream_t copy) {
     }
     if (B.hbm >= 0) B.hbm -= b;
     tier = 0;
+    // pieces come from one stream at every call site; should another add
+    // some, it takes over the earlier ones so the latest record covers all
+    const hipStream_t cs = at::hip::getCurrentHIPStream(dev_.index()).stream();
+    if (cs != hbm_stream_) hbm_written_.wait_on(cs, "mrhip spool: HBM tier hand-off failed");
+    hbm_written_.record(cs, "mrhip spool: HBM tier event failed");
+    hbm_stream_ = cs;
     st_.hbm_bytes += b;
   } else if (B.host < 0 || B.host >= b) {
     // the host tier (pinned when a GPU will read it back); a device piece
@@ -628,7 +620,7 @@ void Spool::add(const KV& piece, hipStream_t copy) {
     // the disk tier off the caller's path: drain into pinned memory on the
     // copy stream, then a background thread writes and maps the file
     KV hp;
-    std::shared_ptr<DrainEvent> done = drain_to_pinned(piece, copy, &hp);
+    std::shared_ptr<Event> done = drain_to_pinned(piece, copy, &hp);
     writing_.emplace_back(pieces_.size(), DiskWriter::get().submit(std::move(hp), std::move(done), next_path()));
     p = KV();  // filled in by sync()
     tier = 2;
@@ -653,18 +645,19 @@ void Spool::clear() {
   for (size_t i = 0; i < pieces_.size(); ++i) release(pieces_[i], tier_[i]);
   pieces_.clear();
   tier_.clear();
+  hbm_written_ = Event();
   n_ = bytes_ = 0;
 }
 
 std::vector<KV> Spool::take() {
-  sync();
+  ready();
   std::vector<KV> parts = pieces_;
   clear();
   return parts;
 }
 
 KV Spool::gather_host() {
-  sync();
+  ready();
   if (pieces_.empty()) {
     clear();
     return empty_kv(at::Device(at::kCPU), 0, 0);
@@ -681,7 +674,7 @@ KV Spool::gather_host() {
 }
 
 KV Spool::gather() {
-  sync();
+  ready();
   SpoolBudget& B = *cfg_.budget;
   if (dev_.is_cuda()) {
     // what the tiers would hold once this spool's own shares are returned

@@ -16,6 +16,14 @@
 //                is deleted when the last tensor viewing it is freed.
 // Budgets are shared by every spool of one op (SpoolBudget), so M partition
 // spools together never exceed the op's host budget.
+//
+// Streams (streams.h): add() takes a piece as the current stream wrote it.
+// What take(), pieces(), gather() and gather_host() return may be read on the
+// stream that is current at THAT call: they wait for the drains and file
+// writes, and, if the spool holds HBM-tier pieces, make that stream wait for
+// the stream that added them and mark the pieces as used on it — so a reader
+// on a side stream may drop the pieces right after queueing its copies. A
+// spool without HBM-tier pieces queues nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +35,7 @@
 #include <vector>
 
 #include "kv.h"
+#include "streams.h"
 
 namespace mrh {
 
@@ -72,24 +81,14 @@ struct WriterStats {
 WriterStats spool_writer_stats();
 void spool_writer_reset_peak();
 
-// a device->host drain's completion event, shared by every spool holding a
-// piece of the drained buffer (destroyed with the last holder)
-struct DrainEvent {
-  hipEvent_t e = nullptr;
-  ~DrainEvent() {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
 // the device KV `dev_kv` copied into one pinned host KV on stream `copy`,
 // ordered after the work queued so far on the current stream; the returned
-// event completes with the copy
-std::shared_ptr<DrainEvent> drain_to_pinned(const KV& dev_kv, hipStream_t copy, KV* host_out);
-// building blocks of asynchronous drains: `copy` waits for the work queued so
-// far on the current stream; `t` (device) copied into new pinned memory on
-// `copy` (the source kept alive until the copy ran); an event recorded on `s`
-void fence_after_current(hipStream_t copy);
+// event completes with the copy and is shared by every spool holding a piece
+// of the drained buffer
+std::shared_ptr<Event> drain_to_pinned(const KV& dev_kv, hipStream_t copy, KV* host_out);
+// one tensor of such a drain: `t` (device) copied into new pinned memory on
+// `copy`, which the caller ordered behind t's writer (streams.h order_after)
 at::Tensor drain_tensor(const at::Tensor& t, hipStream_t copy);
-std::shared_ptr<DrainEvent> record_event(hipStream_t s);
 
 class Spool {
  public:
@@ -108,10 +107,10 @@ class Spool {
   void add(const KV& piece, hipStream_t copy = nullptr);
   // a piece of a host buffer still being drained (drain_to_pinned): host
   // tier, counted against the host budget, readable once `ev` completes
-  void add_drained(const KV& host_piece, const std::shared_ptr<DrainEvent>& ev);
+  void add_drained(const KV& host_piece, const std::shared_ptr<Event>& ev);
   // the same piece for the disk tier: a background thread waits for `ev`,
   // then writes and maps the file (no host budget taken)
-  void add_drained_to_disk(const KV& host_piece, const std::shared_ptr<DrainEvent>& ev);
+  void add_drained_to_disk(const KV& host_piece, const std::shared_ptr<Event>& ev);
   // host budget bytes left to the spools sharing this one's budget (< 0: unlimited)
   int64_t host_room() const { return cfg_.budget->host; }
   // wait for the asynchronous drains
@@ -120,7 +119,7 @@ class Spool {
   int64_t bytes() const { return bytes_; }
   bool empty() const { return pieces_.empty(); }
   const std::vector<KV>& pieces() {
-    sync();
+    ready();
     return pieces_;
   }
   // every piece as one KV: in HBM if the total fits the HBM tier, else in
@@ -138,16 +137,23 @@ class Spool {
  private:
   std::string next_path() const;
   void release(const KV& piece, int tier);
+  // before every read: sync(), then the hand-off of the HBM tier to the
+  // current stream (the rule at the top)
+  void ready();
 
   at::Device dev_;
   SpoolConfig cfg_;
   std::vector<KV> pieces_;
   std::vector<int> tier_;  // 0 HBM, 1 pinned host, 2 disk
-  std::vector<std::shared_ptr<DrainEvent>> pending_;
+  std::vector<std::shared_ptr<Event>> pending_;
   // disk-tier pieces being written by a background thread (index into
   // pieces_, the file-backed KV): the device piece drained into pinned
   // memory on the copy stream, then written and mapped off the caller's path
   std::vector<std::pair<size_t, std::future<KV>>> writing_;
+  // recorded behind every HBM-tier piece on the stream that added it (the
+  // latest record covers the earlier ones); unset while the tier is empty
+  Event hbm_written_;
+  hipStream_t hbm_stream_ = nullptr;
   int64_t n_ = 0, bytes_ = 0;
   SpoolStats st_;
 };
