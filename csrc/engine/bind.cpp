@@ -946,6 +946,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     SsspRelax r = ssspmr_relax(m);
     return py::make_tuple(r.ekeys, r.edges, r.pkeys, r.paths);
   });
+  // pagerank_mr callbacks (contrib / ranks: double bits in int64 words)
+  m.def("prmr_scatter", [](const KMV& m) {
+    PrScatter r = prmr_scatter(m);
+    return py::make_tuple(r.ekeys, r.edges, r.ckeys, r.contrib, r.dangling);
+  });
+  m.def("prmr_update", [](const KMV& m, double base, double alpha, double dterm) {
+    PrUpdate r = prmr_update(m, base, alpha, dterm);
+    return py::make_tuple(r.ranks, r.delta);
+  });
   m.def("lubymr_random", &lubymr_random);
   m.def("lubymr_edge_winner", &lubymr_edge_winner);
   m.def("lubymr_vert", [](const KMV& m, bool loser) {

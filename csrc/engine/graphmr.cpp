@@ -1,12 +1,15 @@
-// sssp_mr / luby_find_mr callback ops (kernels: csrc/kernels/graphmr.hip) with
-// host twins of identical semantics. The OINK commands sssp_mr and
-// luby_find_mr (commands.cpp) run the reference's MapReduce pipelines
-// (oink/sssp.cpp:88-152, oink/luby_find.cpp:53-97) with these as their batch
-// callbacks.
+// sssp_mr / luby_find_mr / pagerank_mr callback ops (kernels:
+// csrc/kernels/graphmr.hip, prmr.hip) with host twins of identical semantics.
+// The OINK commands sssp_mr and luby_find_mr (commands.cpp) run the
+// reference's MapReduce pipelines (oink/sssp.cpp:88-152,
+// oink/luby_find.cpp:53-97) with these as their batch callbacks; pagerank_mr
+// runs the iteration of oinkdoc/pagerank.txt the same way.
 #include "graphmr.h"
 
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <vector>
@@ -210,6 +213,140 @@ SsspRelax ssspmr_relax(const KMV& m) {
   r.edges = longs(ev, 2);
   r.pkeys = longs(pk, 1);
   r.paths = longs(pv, 3);
+  return r;
+}
+
+// ====================================================================== pagerank_mr
+
+namespace {
+constexpr const char* kOneRankScatter = "pagerank_mr scatter: one RANK per vertex";
+constexpr const char* kOneRankUpdate = "pagerank_mr update: one RANK per vertex";
+at::Device kmv_device(const KMV& m) { return m.seg.defined() ? m.seg.device() : at::Device(at::kCPU); }
+// the segred carries (launch.h prmr_carry_entries) of sums over n values
+std::pair<at::Tensor, at::Tensor> pr_carries(int64_t n, at::Device dev) {
+  const int64_t nc = (int64_t)k::prmr_carry_entries(n);
+  return {at::empty({nc}, opt(dev, at::kLong)), at::empty({nc}, opt(dev, at::kDouble))};
+}
+}  // namespace
+
+PrScatter prmr_scatter(const KMV& m) {
+  const at::Device dev = kmv_device(m);
+  PrScatter r;
+  if (m.nkey == 0) {
+    r.ekeys = r.ckeys = r.contrib = at::empty({0}, opt(dev, at::kLong));
+    r.edges = at::empty({0, 2}, opt(dev, at::kLong));
+    return r;
+  }
+  at::Tensor keys = keys64(m, 8, "pagerank_mr scatter: 8-byte vertex keys");
+  // fixed-width values are one kind only: a lone RANK per key, or no RANK at all
+  need(m.vw == 24 || m.vw < 0, kOneRankScatter);
+  const int64_t* seg = P0<int64_t>(m.seg);
+  const int64_t* kp = P0<int64_t>(keys);
+  const Vals V = vals_of(m);
+  if (dev.is_cuda()) {
+    const hipStream_t st = cur();
+    at::Tensor sid = segment_ids(m.seg, m.nkey, m.nval);
+    at::Tensor rank = filled(m.nkey, dev, 0), cnt = filled(m.nkey, dev, 0);
+    at::Tensor flag = at::empty({m.nval + m.nkey}, opt(dev, at::kLong));
+    at::Tensor misc = at::empty({4}, opt(dev, at::kLong));  // one-segment bounds [2], the dangling sum
+    auto [cs, cv] = pr_carries(std::max(m.nkey, m.nval), dev);
+    double* rk = reinterpret_cast<double*>(P0<int64_t>(rank));
+    double* dsum = reinterpret_cast<double*>(P0<int64_t>(misc) + 2);
+    k::prmr_scatter_mark(seg, m.nkey, V.voff, V.vw, V.vd, P0<int64_t>(sid), m.nval, rk,
+                         reinterpret_cast<unsigned long long*>(P0<int64_t>(cnt)), P0<int64_t>(flag), P0<int64_t>(misc),
+                         dsum, P0<int64_t>(cs), P0<double>(cv), st);
+    at::Tensor pos = exclusive_scan(flag);
+    int64_t tot = 0;
+    read_small(st, {{P0<int64_t>(pos) + m.nval + m.nkey, &tot, 8}, {dsum, &r.dangling, 8}});
+    need((tot >> 40) == 0, kOneRankScatter);  // keys without exactly one RANK add 1 << 40 each
+    const int64_t ne = tot;
+    r.ekeys = at::empty({ne}, opt(dev, at::kLong));
+    r.edges = at::empty({ne, 2}, opt(dev, at::kLong));
+    r.ckeys = at::empty({ne}, opt(dev, at::kLong));
+    r.contrib = at::empty({ne}, opt(dev, at::kLong));
+    if (ne)
+      k::prmr_scatter_emit(V.voff, V.vd, P0<int64_t>(sid), kp, P0<int64_t>(pos), rk, m.nval, P0<int64_t>(r.ekeys),
+                           P0<int64_t>(r.edges), P0<int64_t>(r.ckeys), P0<int64_t>(r.contrib), st);
+    return r;
+  }
+  std::vector<int64_t> ek, ev, ck, cc;
+  for (int64_t s = 0; s < m.nkey; ++s) {
+    int nrank = 0;
+    double rk = 0.0;
+    for (int64_t j = seg[s]; j < seg[s + 1]; ++j) {
+      const int64_t l = V.len(j);
+      if (l == 24) {
+        rk = ldd(V.at(j));
+        ++nrank;
+      } else if (l != 16) {
+        nrank += 2;
+      }
+    }
+    need(nrank == 1, kOneRankScatter);
+    if (seg[s + 1] - seg[s] == 1) r.dangling += rk;
+    for (int64_t j = seg[s]; j < seg[s + 1]; ++j) {
+      if (V.len(j) != 16) continue;
+      const int64_t vj = ld8(V.at(j)), wb = ld8(V.at(j) + 8);
+      ek.push_back(kp[s]);
+      ev.insert(ev.end(), {vj, wb});
+      ck.push_back(vj);
+      cc.push_back(bits(dbl(wb) * rk));
+    }
+  }
+  r.ekeys = longs(ek, 1);
+  r.edges = longs(ev, 2);
+  r.ckeys = longs(ck, 1);
+  r.contrib = longs(cc, 1);
+  return r;
+}
+
+PrUpdate prmr_update(const KMV& m, double base, double alpha, double dterm) {
+  const at::Device dev = kmv_device(m);
+  PrUpdate r;
+  r.ranks = at::empty({m.nkey, 3}, opt(dev, at::kLong));
+  if (m.nkey == 0) return r;
+  keys64(m, 8, "pagerank_mr update: 8-byte vertex keys");
+  need(m.vw == 24 || m.vw < 0, kOneRankUpdate);
+  const int64_t* seg = P0<int64_t>(m.seg);
+  const Vals V = vals_of(m);
+  if (dev.is_cuda()) {
+    const hipStream_t st = cur();
+    at::Tensor sid = segment_ids(m.seg, m.nkey, m.nval);
+    at::Tensor ridx = filled(m.nkey, dev, 0xFF), cnt = filled(m.nkey + 1, dev, 0);  // cnt[nkey]: the bad keys
+    at::Tensor sum = at::empty({m.nkey}, opt(dev, at::kDouble)), dcol = at::empty({m.nkey}, opt(dev, at::kDouble));
+    at::Tensor misc = at::empty({4}, opt(dev, at::kLong));  // one-segment bounds [2], the delta
+    auto [cs, cv] = pr_carries(std::max(m.nkey, m.nval), dev);
+    double* delta = reinterpret_cast<double*>(P0<int64_t>(misc) + 2);
+    auto* cu = reinterpret_cast<unsigned long long*>(P0<int64_t>(cnt));
+    k::prmr_update(seg, m.nkey, V.voff, V.vw, V.vd, P0<int64_t>(sid), m.nval, base, alpha, dterm, P0<int64_t>(ridx),
+                   cu, P0<double>(sum), P0<int64_t>(r.ranks), P0<double>(dcol), cu + m.nkey, P0<int64_t>(misc), delta,
+                   P0<int64_t>(cs), P0<double>(cv), st);
+    int64_t nbad = 0;
+    read_small(st, {{cu + m.nkey, &nbad, 8}, {delta, &r.delta, 8}});
+    need(nbad == 0, kOneRankUpdate);
+    return r;
+  }
+  int64_t* out = P0<int64_t>(r.ranks);
+  for (int64_t s = 0; s < m.nkey; ++s) {
+    int nrank = 0;
+    double rk = 0.0, sum = 0.0;
+    for (int64_t j = seg[s]; j < seg[s + 1]; ++j) {
+      const int64_t l = V.len(j);
+      if (l == 8) {
+        sum += ldd(V.at(j));
+      } else if (l == 24) {
+        rk = ldd(V.at(j));
+        ++nrank;
+      } else {
+        nrank += 2;
+      }
+    }
+    need(nrank == 1, kOneRankUpdate);
+    const double rn = base + alpha * (sum + dterm);
+    out[3 * s] = bits(rn);
+    out[3 * s + 1] = out[3 * s + 2] = 0;
+    r.delta += std::fabs(rn - rk);
+  }
   return r;
 }
 

@@ -1,6 +1,7 @@
-// sssp_mr and luby_find_mr callback ops (graphmr.cpp; kernels
-// csrc/kernels/graphmr.hip), for the OINK commands that run the reference's
-// MapReduce formulations (oink/sssp.cpp:88-152, oink/luby_find.cpp:53-97).
+// sssp_mr, luby_find_mr and pagerank_mr callback ops (graphmr.cpp; kernels
+// csrc/kernels/graphmr.hip, prmr.hip), for the OINK commands that run the
+// reference's MapReduce formulations (oink/sssp.cpp:88-152,
+// oink/luby_find.cpp:53-97) and PageRank's (oinkdoc/pagerank.txt).
 // Records are int64 words: DISTANCE {pred, wt bits, current}, EDGEVALUE
 // {v, wt bits}, ERAND {vi, ri bits, vj, rj bits}, VRAND {v, r bits}, VFLAG
 // {v, r bits, flag}. Each op has a host twin of identical semantics.
@@ -27,6 +28,27 @@ struct SsspRelax {
   at::Tensor ekeys, edges, pkeys, paths;
 };
 SsspRelax ssspmr_relax(const KMV& m);
+
+// pagerank_mr (commands.cpp; kernels csrc/kernels/prmr.hip). Records: EDGEW
+// {vj, w bits} 16 B, CONTRIB {x bits} 8 B, RANK {r bits, 0, 0} 24 B. Every
+// group holds exactly one RANK (else both ops throw "one RANK per vertex").
+// scatter, over vertex -> {EDGEW x d, RANK} groups: the edges re-emitted
+// (ekeys [e], edges [e,2]), a contribution w * r per edge keyed by its target
+// (ckeys [e], contrib [e] double bits), and the summed rank of the keys
+// without an EDGEW (dangling)
+struct PrScatter {
+  at::Tensor ekeys, edges, ckeys, contrib;
+  double dangling = 0.0;
+};
+PrScatter prmr_scatter(const KMV& m);
+// update, over vertex -> {CONTRIB x k, RANK} groups (k >= 0): ranks [nkey,3] =
+// RANK{r' = base + alpha * (sum of the CONTRIBs + dterm)} and delta = the sum
+// of |r' - r|; base = (1 - alpha) / N, dterm = D / N
+struct PrUpdate {
+  at::Tensor ranks;
+  double delta = 0.0;
+};
+PrUpdate prmr_update(const KMV& m, double base, double alpha, double dterm);
 
 // map_vert_random (oink/luby_find.cpp:120-136): edges [n,2] -> ERAND [m,4]
 // with drand48() after srand48(v + seed) per end; self loops dropped

@@ -437,6 +437,32 @@ void luby_edges_emit(const int64_t* seg, int64_t nkey, const int64_t* keys, cons
                      const uint8_t* vd, int64_t nval, const int64_t* pf, int64_t* kf, int64_t* kn, hipStream_t s);
 void luby_mis_emit(const int64_t* keys, int64_t nkey, const int64_t* pos, int64_t* out, hipStream_t s);
 
+// ---------------------------------------------------------------- prmr.hip
+// pagerank_mr callbacks: vertex -> {EDGEW 16 B, RANK 24 B} (scatter) and
+// vertex -> {CONTRIB 8 B, RANK 24 B} (update) groups; sid = the key index of
+// every value; voff may be null for fixed-width values of vw bytes.
+// cs / cv: prmr_carry_entries(max(nkey, nval)) entries each (segred.h carries)
+size_t prmr_carry_entries(int64_t n);
+// rank = 0, cnt = 0 on entry. flag [nval + nkey]: 1 per EDGEW value, then
+// 1 << 40 per key that does not hold exactly one RANK (one scan total carries
+// both). dsum[0] = the ranks of the keys without an EDGEW, summed in a fixed
+// order; oneseg: 2 words of scratch
+void prmr_scatter_mark(const int64_t* seg, int64_t nkey, const int64_t* voff, int64_t vw, const uint8_t* vd,
+                       const int64_t* sid, int64_t nval, double* rank, unsigned long long* cnt, int64_t* flag,
+                       int64_t* oneseg, double* dsum, int64_t* cs, double* cv, hipStream_t s);
+// pos = exclusive scan of flag: (vi, EDGEW) back and (vj, w * rank[vi]) out, in value order
+void prmr_scatter_emit(const int64_t* voff, const uint8_t* vd, const int64_t* sid, const int64_t* keys,
+                       const int64_t* pos, const double* rank, int64_t nval, int64_t* ekeys, int64_t* edges,
+                       int64_t* ckeys, int64_t* contrib, hipStream_t s);
+// ridx = -1, cnt = 0, nbad = 0 on entry. ranks [nkey,3] = RANK{base + alpha *
+// (sum of the key's CONTRIBs + dterm)}; delta[0] = sum |r' - r| in a fixed
+// order; nbad = keys that do not hold exactly one RANK; sum, dcol [nkey] and
+// oneseg [2] are scratch
+void prmr_update(const int64_t* seg, int64_t nkey, const int64_t* voff, int64_t vw, const uint8_t* vd,
+                 const int64_t* sid, int64_t nval, double base, double alpha, double dterm, int64_t* ridx,
+                 unsigned long long* cnt, double* sum, int64_t* ranks, double* dcol, unsigned long long* nbad,
+                 int64_t* oneseg, double* delta, int64_t* cs, double* cv, hipStream_t s);
+
 // ---------------------------------------------------------------- trimr.hip
 // tri_find_mr callbacks (oink/tri_find.cpp:104-325); edge rows are int64
 // pairs, degree rows int32 pairs

@@ -1013,6 +1013,122 @@ class PageRankCmd : public Command {
   }
 };
 
+// pagerank_mr tol maxiter alpha -i edges -o file mr: the same iteration as
+// `pagerank` (oinkdoc/pagerank.txt; gpu_mapreduce_amd/models/pagerank.py), in
+// float64, as the MapReduce the plan is an optimisation of — every iteration
+// re-groups the edges with the ranks and the contributions with the ranks on
+// the generic engine, with sssp_mr's op vocabulary (open(1) / kv_open / close
+// appends, compress as join and as combiner, aggregate, Allreduce
+// termination). Records (graphmr.h): EDGEW {vj, w} 16 B, CONTRIB {x} 8 B, RANK
+// {r, 0, 0} 24 B; both joins tell their two kinds of value apart by length.
+//   set-up   out-degrees by degree_weight's op sequence (edge_to_vertex_pair,
+//            collate, a reduce that emits vi -> EDGEW{vj, 1/deg}); mredge
+//            aggregated to owner(vi); mrrank = v -> RANK{1/N} for every id in
+//            [0, N), aggregated the same way
+//   scatter  mrrank's pairs appended to mredge; compress: vi -> {EDGEW x d,
+//            RANK} re-emits the edges and sends (vj, CONTRIB{w r_vi}) into mrc;
+//            keys without an EDGEW add their rank to the dangling mass D
+//   combine  (nprocs > 1) mrc compressed with a per-vj sum, then aggregated
+//   update   mrc's pairs appended to mrrank; compress: v -> {CONTRIB x k, RANK}
+//            emits RANK{(1-alpha)/N + alpha (sum + D/N)} and adds |r' - r|
+// Both compress callbacks are batch callbacks on device tensors (prmr.hip);
+// under a page budget they run once per piece, so D and the delta accumulate.
+class PageRankMR : public Command {
+ public:
+  PageRankMR(Oink& o) : Command(o) { ninputs = noutputs = 1; }
+  double tol = 0, alpha = 0.85;
+  int maxiter = 0;
+  void params(const Args& a) override {
+    if (a.size() != 3) throw Error("Illegal pagerank_mr command");
+    tol = dval(a[0], "pagerank_mr");
+    maxiter = (int)lval(a[1], "pagerank_mr");
+    alpha = dval(a[2], "pagerank_mr");
+  }
+  void run() override {
+    const at::Device dev = comm->device();
+    MapReduce& mre = obj.input(1, rd(parse_edge), rc(parse_edge));
+    mre.flatten();
+    const int64_t N =
+        nvert_global(*comm, mre.kv ? edges_of(*mre.kv) : at::empty({0, 2}, opt(dev, at::kLong)));
+    // vi -> EDGEW{vj, 1/outdeg(vi)}: degree_weight's op sequence, its join folded into the reduce
+    MapReduce& mredge = obj.create_mr();
+    mredge.map_mr_batch(mre, edge_to_vertex_pair);
+    mredge.collate();
+    mredge.reduce_batch([](const KMV& m, KeyValue& kv) {
+      if (!m.nval) return;
+      at::Tensor sid = kmv_sid(m);
+      at::Tensor w = at::reciprocal(kmv_lens(m).to(at::kDouble)).index_select(0, sid);
+      add_tensors(kv, m.keys.kdata.view(at::kLong).index_select(0, sid),
+                  at::stack({m.vdata.view(at::kLong), w.view(at::kLong)}, 1));
+    });
+    mredge.aggregate();
+    // v -> RANK{1/N} for every id in [0, N), each rank its slice; same owners as mredge
+    MapReduce& mrrank = obj.create_mr();
+    const int P = nprocs;
+    mrrank.map(P, [&](int t, KeyValue& kv) {
+      const int64_t lo = (int64_t)t * N / P, hi = (int64_t)(t + 1) * N / P;
+      if (hi <= lo) return;
+      at::Tensor r = at::zeros({hi - lo, 3}, opt(dev, at::kLong));
+      r.select(1, 0).copy_(at::full({hi - lo}, 1.0 / (double)N, opt(dev, at::kDouble)).view(at::kLong));
+      add_tensors(kv, at::arange(lo, hi, opt(dev, at::kLong)), r);
+    });
+    mrrank.aggregate();
+    MapReduce& mrc = obj.create_mr();
+    MapReduce& mrwalk = obj.create_mr();  // reads another MR's pairs, emits nothing
+    const double base = N > 0 ? (1.0 - alpha) / (double)N : 0.0;
+    double delta = 0.0;
+    int niter = 0;
+    while (niter < maxiter) {
+      ++niter;
+      mredge.open(1);
+      mrwalk.map_mr_batch(mrrank, [&](const KV& src, KeyValue&) {
+        if (src.n) mredge.kv_open().add_kv(src);
+      });
+      mredge.close();
+      mrc.open();
+      double dangling = 0.0;
+      mredge.compress_batch([&](const KMV& m, KeyValue& kv) {  // scatter
+        if (!m.nkey) return;
+        PrScatter s = prmr_scatter(m);
+        dangling += s.dangling;
+        if (!s.ekeys.numel()) return;
+        add_tensors(kv, s.ekeys, s.edges);
+        add_tensors(mrc.kv_open(), s.ckeys, s.contrib);
+      });
+      mrc.close();
+      const double D = comm->allreduce_f64(dangling, Comm::SUM);
+      if (nprocs > 1)
+        mrc.compress_batch([](const KMV& m, KeyValue& kv) {  // combiner
+          if (m.nkey) kv.add_kv(reduce_builtin(m, "sum", "double"));
+        });
+      mrc.aggregate();
+      mrrank.open(1);
+      mrc.map_mr_batch(mrc, [&](const KV& src, KeyValue&) {
+        if (src.n) mrrank.kv_open().add_kv(src);
+      });
+      mrrank.close();
+      double d = 0.0;
+      mrrank.compress_batch([&](const KMV& m, KeyValue& kv) {  // update
+        if (!m.nkey) return;
+        PrUpdate u = prmr_update(m, base, alpha, D / (double)N);
+        d += u.delta;
+        add_tensors(kv, m.keys.kdata.view(at::kLong), u.ranks);
+      });
+      delta = comm->allreduce_f64(d, Comm::SUM);
+      if (tol > 0 && delta < tol) break;
+    }
+    MapReduce& mrr = obj.create_mr();
+    mrr.map_mr_batch(mrrank, [](const KV& src, KeyValue& kv) {
+      if (!src.n) return;
+      at::Tensor r = src.vdata.view(at::kLong).view({-1, 3}).select(1, 0).contiguous();
+      add_tensors(kv, src.kdata.view(at::kLong), r.view(at::kDouble));
+    });
+    obj.output(1, mrr, print_vertex_double);
+    message(fmt("PageRank_MR: %" PRId64 " vertices, %d iterations, L1 delta %g", N, niter, delta));
+    obj.cleanup();
+  }
+};
+
 template <typename T>
 CommandFactory factory() {
   return [](Oink& o) { return std::unique_ptr<Command>(new T(o)); };
@@ -1042,6 +1158,7 @@ struct Registrar {
     r["sssp_mr"] = factory<SSSPMR>();
     r["luby_find_mr"] = factory<LubyFindMR>();
     r["pagerank"] = factory<PageRankCmd>();
+    r["pagerank_mr"] = factory<PageRankMR>();
   }
 } registrar;
 
