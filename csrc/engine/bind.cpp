@@ -506,6 +506,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("sort_values_device", &MR::sort_values_device, py::arg("code"), py::arg("bits") = 64,
            py::call_guard<py::gil_scoped_release>())
+      .def("sort_multivalues_device", &MR::sort_multivalues_device, py::arg("code"), py::arg("bits") = 64,
+           py::call_guard<py::gil_scoped_release>())
       .def("compress_batch",
            [](MR& r, py::function fn) {
              py::gil_scoped_release nogil;
@@ -970,6 +972,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("device_functor_source", &devfn::full_source, py::arg("code"), py::arg("reduce"));
   m.def("device_sortkey_check", &devfn::compile_check_sortkey, py::arg("code"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("device_compare_check", &devfn::compile_check_compare, py::arg("code"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("device_compare_tile", &devfn::compare_tile);
   m.def("host_arena_reserve", &hostarena::reserve, py::call_guard<py::gil_scoped_release>());
   m.def("host_arena_stats", [] {
     hostarena::Stats s = hostarena::stats();

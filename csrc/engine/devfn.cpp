@@ -9,6 +9,8 @@
 //
 // A uniform output width (every key, every value the same length) turns
 // into a fixed-width KV, so later ops keep their fixed-key fast paths.
+// The two sort functors have kernels of their own: mrd_sortkey (a 64-bit key
+// per row for the radix sort) and the comparator merge sort (kCompareKernels).
 // Modules are cached per (device, kind, code).
 #include "devfn.h"
 
@@ -16,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <functional>
 #include <memory>
@@ -279,16 +282,191 @@ mrd_sortkey(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, mrd::
 }
 )MRD";
 
+// kind 4: a comparator functor, __device__ int mr_compare(mrd::Bytes a, mrd::Bytes b)
+// (MR-MPI's contract: < 0 a first, 0 equal, > 0 b first). A stable merge sort
+// over a u32 row-index permutation; the payload moves once afterwards (gather).
+//
+//   mrd_cmp_blocksort  one workgroup per tile of MRD_CMP_T rows: every thread
+//                      sorts its own rows in registers, then merge-path merges
+//                      in LDS double the run width until the tile is one run
+//   mrd_cmp_merge      one launch per pass, runs of W -> runs of 2W between two
+//                      index buffers; one workgroup per output tile: its split
+//                      on the merge-path diagonal (binary search on global
+//                      rows), the two sub-ranges into LDS, then the tile step
+//
+// Rows are ordered by less(i, j) = c < 0 || (c == 0 && i < j), c = mr_compare
+// (row i, row j), after the optional segment ids: a total order, so stability
+// and the merge-path splits need no special cases. The pass count depends on
+// n alone (no host read between passes) and no workgroup waits for another.
+//
+// Memory safety does not depend on what mr_compare returns: every binary
+// search runs a bounded number of steps inside [max(0, d - lb), min(d, la)],
+// an end split is clamped to what its start split leaves reachable, and every
+// merge consumes exactly the counts its two splits give it. So the index
+// buffers only ever hold row numbers that were put in, and a comparator that
+// is not a strict weak order gives an unspecified order (possibly with
+// repeated rows), never an access outside the columns.
+const char* kCompareKernels = R"MRD(
+// ---- mrd comparator merge sort ----
+namespace mrd {
+typedef unsigned int u32;
+enum { CMP_T = MRD_CMP_T, CMP_PER = MRD_CMP_T / 256 };
+struct Cmp {
+  const u8* d;
+  const i64* off;
+  i64 w;
+  const i64* sid;  // segment id of every row, compared first (null: no segments)
+  __device__ Bytes row(u32 i) const { return off ? Bytes{d + off[i], off[i + 1] - off[i]} : Bytes{d + i * w, w}; }
+  __device__ bool less(u32 i, u32 j) const {
+    if (sid) {
+      const i64 a = sid[i], b = sid[j];
+      if (a != b) return a < b;
+    }
+    const int c = mr_compare(row(i), row(j));
+    return c < 0 || (c == 0 && i < j);
+  }
+};
+// merge path: how many of the first d rows of merge(A[0, la), B[0, lb)) come
+// from A. At most 64 steps, every index inside its run whatever less() says.
+template <class I>
+__device__ inline I cmp_split(const Cmp& c, const u32* A, I la, const u32* B, I lb, I d) {
+  I lo = d > lb ? d - lb : 0, hi = d < la ? d : la;
+  while (lo < hi) {
+    const I mid = (lo + hi) >> 1;
+    if (c.less(B[d - 1 - mid], A[mid])) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+// an end split as the start split a on diagonal d allows it: a <= a1 <= la,
+// and the B side likewise (a no-op for a strict weak order)
+template <class I>
+__device__ inline I cmp_clamp(I a1, I a, I d, I d1, I la, I lb) {
+  const I lo = a > d1 - lb ? a : d1 - lb, hi = a + (d1 - d) < la ? a + (d1 - d) : la;
+  return a1 < lo ? lo : a1 > hi ? hi : a1;
+}
+// one merge step of a tile in LDS: the runs A = src[s, s + la) and
+// B = src[s + la, s + la + lb) into dst[s, ..); thread t writes the tile's
+// rows [CMP_PER * t, CMP_PER * (t + 1)). All 256 threads call it.
+__device__ inline void cmp_merge_tile(const Cmp& c, const u32* src, u32* dst, int* split, int s, int la, int lb) {
+  const int t = threadIdx.x, tot = la + lb;
+  int d = CMP_PER * t - s;
+  d = d < tot ? d : tot;
+  const int d1 = d + CMP_PER < tot ? d + CMP_PER : tot;
+  const u32* A = src + s;
+  const u32* B = A + la;
+  int a = cmp_split<int>(c, A, la, B, lb, d);
+  split[t] = a;
+  __syncthreads();
+  // the end split is the next thread's start (same pair of runs), or the pair's end
+  const int a1 = cmp_clamp<int>(d1 < tot ? split[t + 1] : la, a, d, d1, la, lb);
+  int b = d - a;
+  const int b1 = d1 - a1;
+  for (int k = d; k < d1; ++k) {  // (a1 - a) + (b1 - b) == d1 - k throughout
+    if (a < a1 && (b >= b1 || !c.less(B[b], A[a]))) dst[s + k] = A[a++];
+    else dst[s + k] = B[b++];
+  }
+}
+}  // namespace mrd
+extern "C" __global__ __launch_bounds__(256) void
+mrd_cmp_blocksort(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64* sid, mrd::i64 n, mrd::u32* out) {
+  using namespace mrd;
+  __shared__ u32 buf[2][CMP_T];
+  __shared__ int split[257];
+  const Cmp c{d, off, w, sid};
+  const i64 base = (i64)blockIdx.x * CMP_T;
+  const int cnt = n - base < CMP_T ? (int)(n - base) : CMP_T;
+  const int t = threadIdx.x;
+  // the thread's own rows: odd-even transposition in registers
+  const int m = cnt - CMP_PER * t < 0 ? 0 : cnt - CMP_PER * t < CMP_PER ? cnt - CMP_PER * t : CMP_PER;
+  u32 v[CMP_PER];
+#pragma unroll
+  for (int k = 0; k < CMP_PER; ++k) v[k] = (u32)(base + CMP_PER * t + k);
+#pragma unroll 1
+  for (int r = 0; r < (CMP_PER + 1) / 2; ++r) {
+#pragma unroll
+    for (int k = 0; k + 1 < CMP_PER; k += 2)
+      if (k + 1 < m && c.less(v[k + 1], v[k])) {
+        const u32 x = v[k];
+        v[k] = v[k + 1];
+        v[k + 1] = x;
+      }
+#pragma unroll
+    for (int k = 1; k + 1 < CMP_PER; k += 2)
+      if (k + 1 < m && c.less(v[k + 1], v[k])) {
+        const u32 x = v[k];
+        v[k] = v[k + 1];
+        v[k + 1] = x;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < CMP_PER; ++k)
+    if (k < m) buf[0][CMP_PER * t + k] = v[k];
+  int cur = 0;
+  for (int W = CMP_PER; W < CMP_T && W < cnt; W <<= 1) {  // cnt is the workgroup's: a uniform trip count
+    __syncthreads();
+    const int s = CMP_PER * t / (2 * W) * (2 * W);
+    const int la = cnt - s < 0 ? 0 : cnt - s < W ? cnt - s : W;
+    const int lb = cnt - s - W < 0 ? 0 : cnt - s - W < W ? cnt - s - W : W;
+    cmp_merge_tile(c, buf[cur], buf[cur ^ 1], split, s, la, lb);
+    cur ^= 1;
+  }
+  __syncthreads();
+  for (int i = t; i < cnt; i += 256) out[base + i] = buf[cur][i];
+}
+extern "C" __global__ __launch_bounds__(256) void
+mrd_cmp_merge(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64* sid, mrd::i64 n,
+              const mrd::u32* src, mrd::u32* dst, mrd::i64 W) {
+  using namespace mrd;
+  __shared__ u32 buf[2][CMP_T];
+  __shared__ int split[257];
+  __shared__ i64 ends[2];
+  const Cmp c{d, off, w, sid};
+  const int t = threadIdx.x;
+  const i64 g0 = (i64)blockIdx.x * CMP_T;  // this workgroup's output tile: dst[g0, g0 + cnt)
+  const int cnt = n - g0 < CMP_T ? (int)(n - g0) : CMP_T;
+  const i64 s = g0 / (2 * W) * (2 * W);    // its pair of runs: src[s, s + la) and src[s + la, s + la + lb)
+  const i64 la = n - s < W ? n - s : W;
+  const i64 lb = n - s - W < 0 ? 0 : n - s - W < W ? n - s - W : W;
+  if (lb == 0) {  // a last run without a partner: copied through
+    for (int i = t; i < cnt; i += 256) dst[g0 + i] = src[g0 + i];
+    return;
+  }
+  const u32* A = src + s;
+  const u32* B = A + la;
+  const i64 d0 = g0 - s, d1 = d0 + cnt;  // d1 <= la + lb: the tile lies inside the pair
+  if (t == 0) ends[0] = cmp_split<i64>(c, A, la, B, lb, d0);
+  if (t == 64) ends[1] = cmp_split<i64>(c, A, la, B, lb, d1);
+  __syncthreads();
+  const i64 a0 = ends[0], a1 = cmp_clamp<i64>(ends[1], a0, d0, d1, la, lb);
+  const i64 b0 = d0 - a0;
+  const int na = (int)(a1 - a0), nb = cnt - na;  // b0 + nb == d1 - a1 <= lb
+  for (int i = t; i < cnt; i += 256) buf[0][i] = i < na ? A[a0 + i] : B[b0 + (i - na)];
+  __syncthreads();
+  cmp_merge_tile(c, buf[0], buf[1], split, 0, na, nb);
+  __syncthreads();
+  for (int i = t; i < cnt; i += 256) dst[g0 + i] = buf[1][i];
+}
+)MRD";
+
 struct Module {
   hipModule_t mod = nullptr;
   hipFunction_t count = nullptr, write = nullptr;
   hipFunction_t acc_size = nullptr, nchunks = nullptr, chunks = nullptr, merge = nullptr;  // fold tier
 };
 const char* kind_name(int kind) {
-  return kind == 0 ? "mrd_map.hip" : kind == 1 ? "mrd_reduce.hip" : kind == 2 ? "mrd_fold.hip" : "mrd_sortkey.hip";
+  return kind == 0   ? "mrd_map.hip"
+         : kind == 1 ? "mrd_reduce.hip"
+         : kind == 2 ? "mrd_fold.hip"
+         : kind == 3 ? "mrd_sortkey.hip"
+                     : "mrd_compare.hip";
 }
+// rows per workgroup tile of the comparator sort (256 threads, 8 rows each)
+constexpr int64_t kCompareTile = 2048;
 std::string source_of(const std::string& code, int kind) {
   if (kind == 3) return std::string(kDevicePrelude) + code + "\n" + kSortKernel;
+  if (kind == 4)
+    return "#define MRD_CMP_T " + std::to_string(kCompareTile) + "\n" + kDevicePrelude + code + "\n" + kCompareKernels;
   return "#define MRD_REDUCE " + std::to_string(kind) + "\n" + kDevicePrelude + code + "\n" + kKernels;
 }
 
@@ -328,6 +506,15 @@ const Module& module_for(const std::string& code, int kind, int device) {
         hipModuleGetFunction(&m->count, m->mod, "mrd_sortkey") != hipSuccess) {
       (void)hipGetLastError();
       throw std::runtime_error("mrhip: loading the sort-key functor's code object failed");
+    }
+    return *cache.emplace(key, std::move(m)).first->second;
+  }
+  if (kind == 4) {  // count = the tile sort, write = the merge pass
+    if (hipModuleLoadData(&m->mod, obj.data()) != hipSuccess ||
+        hipModuleGetFunction(&m->count, m->mod, "mrd_cmp_blocksort") != hipSuccess ||
+        hipModuleGetFunction(&m->write, m->mod, "mrd_cmp_merge") != hipSuccess) {
+      (void)hipGetLastError();
+      throw std::runtime_error("mrhip: loading the comparator functor's code object failed");
     }
     return *cache.emplace(key, std::move(m)).first->second;
   }
@@ -477,6 +664,59 @@ std::pair<at::Tensor, at::Tensor> sort_keys_of(const at::Tensor& data, const at:
     launch(m.count, n, args, at::hip::getCurrentHIPStream());
   }
   return {key.narrow(0, 0, n), idx.narrow(0, 0, n)};
+}
+
+int sort_kind_of(const std::string& code) {
+  if (code.find("mr_sortkey") != std::string::npos) return 3;
+  if (code.find("mr_compare") != std::string::npos) return 4;
+  throw std::runtime_error(
+      "mrhip: a device sort functor defines `unsigned long long mr_sortkey(mrd::Bytes)` (radix sort by a 64-bit key) "
+      "or `int mr_compare(mrd::Bytes, mrd::Bytes)` (merge sort by a comparator); the code has neither");
+}
+
+int64_t compile_check_compare(const std::string& code) {
+  return (int64_t)compile(source_of(code, 4), kind_name(4)).size();
+}
+
+int64_t compare_tile() { return kCompareTile; }
+
+at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, int64_t n, const at::Tensor& sid,
+                        const std::string& code, at::Device dev) {
+  if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  if (n > (int64_t)UINT32_MAX)
+    throw std::runtime_error("mrhip: the comparator sort indexes rows with 32 bits; " + std::to_string(n) +
+                             " rows are more than 4294967295");
+  if (sid.defined() && sid.numel() < n) throw std::runtime_error("mrhip: compare_perm: fewer segment ids than rows");
+  at::Tensor a = at::empty({std::max<int64_t>(n, 1)}, opt(dev, at::kInt));
+  if (n <= 0) return a.narrow(0, 0, 0);
+  at::Tensor b = n > kCompareTile ? at::empty({n}, opt(dev, at::kInt)) : at::Tensor();
+  const Module& m = module_for(code, 4, dev.index());
+  hipStream_t s = at::hip::getCurrentHIPStream();
+  const unsigned tiles = (unsigned)((n + kCompareTile - 1) / kCompareTile);
+  const uint8_t* d = P0<uint8_t>(data);
+  const int64_t* o = w >= 0 ? nullptr : P0<int64_t>(off);
+  const int64_t* sg = P0<int64_t>(sid);
+  int64_t ww = w >= 0 ? w : 0, nn = n;
+  uint32_t* src = P0<uint32_t>(a);
+  uint32_t* dst = P0<uint32_t>(b);
+  auto go = [&](hipFunction_t f, void** args) {
+    if (hipModuleLaunchKernel(f, tiles, 1, 1, 256, 1, 1, 0, s, args, nullptr) != hipSuccess) {
+      (void)hipGetLastError();
+      throw std::runtime_error("mrhip: device functor launch failed");
+    }
+  };
+  {
+    void* args[] = {&d, &o, &ww, &sg, &nn, &src};
+    go(m.count, args);
+  }
+  // ceil(log2(tiles)) passes, known from n alone: nothing is read back between them
+  for (int64_t W = kCompareTile; W < n; W *= 2) {
+    void* args[] = {&d, &o, &ww, &sg, &nn, &src, &dst, &W};
+    go(m.write, args);
+    std::swap(src, dst);
+    std::swap(a, b);
+  }
+  return a;
 }
 
 int64_t compile_check(const std::string& code, bool reduce) {

@@ -38,6 +38,22 @@ int64_t compile_check(const std::string& code, bool reduce);
 std::pair<at::Tensor, at::Tensor> sort_keys_of(const at::Tensor& data, const at::Tensor& off, int w, int64_t n,
                                                const std::string& code, at::Device dev);
 int64_t compile_check_sortkey(const std::string& code);
+// comparator functor: `__device__ int mr_compare(mrd::Bytes a, mrd::Bytes b)`
+// with MR-MPI's contract (< 0 a before b, 0 equal, > 0 b before a), a strict
+// weak order and a pure function of its arguments: for orders that do not fit
+// a 64-bit key. Returns the stable sorted row permutation [n] int32 (u32 row
+// numbers) of a merge sort that runs in the functor's compiled module. sid
+// (int64 [n], may be undefined) is compared before mr_compare: rows grouped
+// by segment are sorted inside every segment by one call.
+at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, int64_t n, const at::Tensor& sid,
+                        const std::string& code, at::Device dev);
+// compile only; the code object size in bytes. Works without a GPU.
+int64_t compile_check_compare(const std::string& code);
+// rows per workgroup tile of the comparator sort (a power of two)
+int64_t compare_tile();
+// which sort functor the code defines: 3 = mr_sortkey (wins when both names
+// appear), 4 = mr_compare; neither is an error that names both
+int sort_kind_of(const std::string& code);
 // the full source handed to the compiler (prelude + code + kernels)
 std::string full_source(const std::string& code, bool reduce);
 }  // namespace devfn

@@ -1424,12 +1424,17 @@ uint64_t MapReduce::reduce_device(const std::string& code) {
 }
 
 namespace {
-// stable radix sort of the pairs by the functor's 64-bit keys of one column
+// the pairs sorted by a device sort functor over one column, stable:
+// mr_sortkey -> radix sort of its 64-bit keys; mr_compare -> the merge sort
 KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_value, at::Device dev) {
+  const int kind = devfn::sort_kind_of(code);
   if (kv_in.n <= 1) return kv_in;
   const KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
-  auto [key, idx] = by_value ? devfn::sort_keys_of(kv.vdata, kv.voff, kv.vw, kv.n, code, dev)
-                             : devfn::sort_keys_of(kv.kdata, kv.koff, kv.kw, kv.n, code, dev);
+  const at::Tensor& data = by_value ? kv.vdata : kv.kdata;
+  const at::Tensor& off = by_value ? kv.voff : kv.koff;
+  const int w = by_value ? kv.vw : kv.kw;
+  if (kind == 4) return gather(kv, devfn::compare_perm(data, off, w, kv.n, at::Tensor(), code, dev));
+  auto [key, idx] = devfn::sort_keys_of(data, off, w, kv.n, code, dev);
   auto [ks, perm, passes] = radix_sort_pairs(key, idx, 0, std::max(1, std::min(bits, 64)));
   (void)ks;
   (void)passes;
@@ -1455,6 +1460,46 @@ uint64_t MapReduce::sort_values_device(const std::string& code, int bits) {
   kv = sort_by_functor(*kv, code, bits, true, device());
   stats("Sort_values", 0);
   return count(kv->n);
+}
+
+uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
+  start();
+  OpTrace tr_("sort_multivalues", this);
+  enter("sort_multivalues");
+  need_kmv("sort_multivalues");
+  const int kind = devfn::sort_kind_of(code);
+  const at::Device dev = device();
+  if (kmv->nval > 1) {
+    KMV m = *kmv;
+    if (m.seg.device() != dev) {
+      m.keys = kv_to(m.keys, dev);
+      m.vdata = m.vdata.to(dev);
+      if (m.voff.defined()) m.voff = m.voff.to(dev);
+      m.seg = m.seg.to(dev);
+    }
+    at::Tensor perm;
+    if (kind == 4) {
+      // the values are grouped by key already: one sort under (segment id, mr_compare)
+      perm = devfn::compare_perm(m.vdata, m.voff, m.vw, m.nval, segment_ids(m.seg, m.nkey, m.nval), code, dev);
+    } else {
+      // LSD, as mrh::sort_multivalues: stable by the functor's key, then stable by segment id
+      auto [key, idx] = devfn::sort_keys_of(m.vdata, m.voff, m.vw, m.nval, code, dev);
+      auto [ks, perm1, p1] = radix_sort_pairs(key, idx, 0, std::max(1, std::min(bits, 64)));
+      at::Tensor sid_p = segment_ids(m.seg, m.nkey, m.nval).index_select(0, perm1.to(at::kLong));
+      auto [ss, perm2, p2] = radix_sort_pairs(sid_p, perm1, 0, 64);
+      (void)ks;
+      (void)ss;
+      (void)p1;
+      (void)p2;
+      perm = perm2;
+    }
+    at::Tensor noff;
+    m.vdata = gather_rows(m.vdata, m.voff, m.vw, perm, m.vw < 0 ? &noff : nullptr);
+    if (m.vw < 0) m.voff = noff;
+    kmv = m;
+  }
+  stats("Sort_multivalues", 1);
+  return count(kmv_keys());
 }
 
 uint64_t MapReduce::compress_device(const std::string& code) {

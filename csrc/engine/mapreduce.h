@@ -136,9 +136,14 @@ class MapReduce {
   uint64_t map_device_tasks(int64_t ntask, const std::string& code, int addflag = 0);
   uint64_t reduce_device(const std::string& code);
   uint64_t compress_device(const std::string& code);
-  // sort by a device sort-key functor (mr_sortkey: key -> u64 in the wanted order), stable
+  // stable sort by a device sort functor: mr_sortkey (key -> u64 in the wanted
+  // order; radix sort over `bits` bits) or, for orders that do not fit 64
+  // bits, mr_compare (a comparator; merge sort, bits ignored). mr_sortkey
+  // wins when the code names both.
   uint64_t sort_keys_device(const std::string& code, int bits = 64);
   uint64_t sort_values_device(const std::string& code, int bits = 64);
+  // every key's values of the KMV sorted by either functor; returns the global key count
+  uint64_t sort_multivalues_device(const std::string& code, int bits = 64);
   uint64_t convert();
   // convert with the keys' hash64_keys() already computed by the producer
   uint64_t convert_prehashed(const at::Tensor& prehash);

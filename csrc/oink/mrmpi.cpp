@@ -144,10 +144,11 @@ void run_mr_method(Oink& o, int index, const Args& args) {
     std::shared_ptr<MapReduce> src = obj.mrs[j].mr;
     mr.map_mr_batch(*src, it->second, n == 3 ? ival(a[2]) : 0);
   } else if (cmd == "map/device" || cmd == "map/mr/device" || cmd == "reduce/device" || cmd == "compress/device" ||
-             cmd == "sort_keys/device" || cmd == "sort_values/device") {
+             cmd == "sort_keys/device" || cmd == "sort_values/device" || cmd == "sort_multivalues/device") {
     // device functors (csrc/engine/devfn.h), the HIP source read from a file:
     //   map/device ntask file [addflag] | map/mr/device mr file [addflag] |
-    //   reduce/device file | compress/device file | sort_keys/device file [bits] | sort_values/device file [bits]
+    //   reduce/device file | compress/device file | sort_keys/device file [bits] | sort_values/device file [bits] |
+    //   sort_multivalues/device file [bits]
     auto source = [&](const std::string& path) {
       std::ifstream f(path);
       if (!f) throw Error("Cannot open device functor file " + path);
@@ -172,7 +173,8 @@ void run_mr_method(Oink& o, int index, const Args& args) {
       need(1, 2);
       const int bits = n == 2 ? ival(a[1]) : 64;
       if (cmd == "sort_keys/device") mr.sort_keys_device(source(a[0]), bits);
-      else mr.sort_values_device(source(a[0]), bits);
+      else if (cmd == "sort_values/device") mr.sort_values_device(source(a[0]), bits);
+      else mr.sort_multivalues_device(source(a[0]), bits);
     }
   } else if (cmd == "print") {
     if (n == 4) mr.print(ival(a[0]), ival(a[1]), ival(a[2]), ival(a[3]));

@@ -308,15 +308,26 @@ class MapReduce(metaclass=_Counters):
         return self._m.reduce_device(code)
 
     def sort_keys_device(self, code, bits=64):
-        """stable sort by a device sort-key functor: `__device__ unsigned long
-        long mr_sortkey(mrd::Bytes key)` maps each key to a 64-bit key whose
-        unsigned order is the wanted one (a comparator as a key extraction;
-        `bits` low bits are sorted on)."""
+        """stable sort by a device sort functor, in one of two forms.
+        `__device__ unsigned long long mr_sortkey(mrd::Bytes key)` maps each
+        key to a 64-bit key whose unsigned order is the wanted one (a
+        comparator as a key extraction; `bits` low bits are sorted on): the
+        radix sort, the faster form whenever the order fits 64 bits.
+        `__device__ int mr_compare(mrd::Bytes a, mrd::Bytes b)` (< 0 a first,
+        0 equal, > 0 b first; a strict weak order) is for every other order:
+        a merge sort on the GPU, `bits` ignored. Code naming both takes the
+        mr_sortkey form."""
         return self._m.sort_keys_device(code, bits)
 
     def sort_values_device(self, code, bits=64):
-        """sort_keys_device over the values."""
+        """sort_keys_device over the values (either functor form)."""
         return self._m.sort_values_device(code, bits)
+
+    def sort_multivalues_device(self, code, bits=64):
+        """every key's values of the KMV sorted by a device sort functor
+        (mr_sortkey or mr_compare, as sort_keys_device); returns the global
+        key count."""
+        return self._m.sort_multivalues_device(code, bits)
 
     def compress_device(self, code):
         """compress (local groups, no shuffle) with a device reduce functor."""
