@@ -298,7 +298,7 @@ __global__ __launch_bounds__(TNT) void k_kmeans_tr(const float* __restrict__ pts
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           // one select + D+1 FMAs per point: the count rides along as a float
-          // (exact: a lane adds at most ~n / (64 x grid) ones)
+          // (exact: a lane adds at most ~n / (8 x grid) ones)
           const float m = bb[q] == c ? 1.f : 0.f;
           cnt[g] += m;
 #pragma unroll
@@ -631,9 +631,30 @@ void launch(const float* pts, int64_t n, const float* cen, int K, double* acc, h
 
 }  // namespace
 
-// fp32 LDS partials hold at most NT*PTS_PER_THREAD = 2048 points per workgroup,
-// so per-cluster counts are exact and sums lose no more than fp32 rounding of
-// 2048 terms before the fp64 global accumulation.
+// Every kernel above sums in fp32 (LDS or registers) before its fp64 global
+// atomics. A float count is exact while its partial stays below 2^24, and a
+// coordinate sum loses the fp32 rounding of as many terms as the partial
+// holds. Points per fp32 partial, all of them in one cluster at worst:
+//   k_kmeans, k_kmeans_batch  one 2048-point tile per workgroup: <= 2048
+//                             (batch: over BC copies), at any n;
+//   k_kmeans_tr               a lane's registers: 256 points per tile trip,
+//                             256 * ceil(n / (2048 * grid)), grid = 8 x CUs —
+//                             2^24 at n = 2^30 x CUs (2.7e11 with 256 CUs);
+//   k_kmeans_reg              a lane's registers: ceil(n / (1024 * 256)),
+//                             folded in fp64 — 2^24 at n = 2^42;
+//   k_kmeans_priv             a lane's LDS column: ceil(n / (2048 * 128)),
+//                             but the end-of-kernel fold sums the workgroup
+//                             in fp32: ~n / 2048 — 2^24 at n = 2^35 (3.4e10);
+//   k_kmeans_mfma, k_kmeans_accum (LDS partials)
+//                             persistent grid of <= 2048 workgroups, one
+//                             partial each: ~n / 2048 points (4096 at 8 M
+//                             points) — 2^24 at n = 2^35;
+//   k_kmeans_accum (global)   fp64 atomics per point: exact.
+// Of these only the opt-in k_kmeans_priv at D = 1 (137 GB of points, all in
+// one cluster) could meet its limit within one device's 288 GB. Below the
+// limits the counts are exact, and on integer-valued input whose per-cluster
+// sums stay below 2^24 so is every sum (tests/test_kmeans_exact.py relies
+// on that).
 void kmeans_accumulate(const float* pts, int64_t n, int D, const int64_t* idx, int K, double* acc, hipStream_t s) {
   if (n <= 0) return;
   const size_t lds = sizeof(float) * (size_t)K * (D + 1);

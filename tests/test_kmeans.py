@@ -50,12 +50,13 @@ def test_kmeans_job_matches_lloyd():
 @pytest.mark.parametrize("D,K", [(2, 32), (3, 5), (1, 8), (3, 64), (8, 64), (16, 10), (5, 7), (32, 64), (64, 128), (100, 40),
                                  (128, 16), (160, 8)])
 def test_kmeans_map_gpu(D, K):
-    """lane-private accumulator kernel (D <= 3, K * (D+1) <= 184; (3, 64)
-    falls back to the LDS-atomic batched kernel), fused assign + LDS combine
-    kernel (D <= 8), the matrix-core kernel
-    (D <= 128, any K that fits LDS) and the GEMM fallback (D = 160) against
-    the float64 oracle; a point equidistant to two centroids may go either
-    way, so compare with a tolerance on the counts too"""
+    """transposed-reduction kernel (D <= 3, K <= 256: (3, 64) included),
+    fused assign + LDS combine kernel (D in {4, 8} only), the matrix-core
+    kernel (every other D <= 128, D = 5 included, any K that fits LDS) and
+    the GEMM fallback (D = 160) against the float64 oracle; a point
+    equidistant to two centroids may go either way, so compare with a
+    tolerance on the counts too (tests/test_kmeans_exact.py has the exact
+    checks, per kernel route)"""
     p = blobs(300_000, D, K, seed=5, device="cuda")
     c = blobs(K, D, K, seed=6, device="cuda")
     got = _kv_vals(C.kmeans_map(p, c))
