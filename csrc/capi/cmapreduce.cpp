@@ -226,6 +226,23 @@ uint64_t MR_reduce_device(void* p, const char* code) {
 uint64_t MR_compress_device(void* p, const char* code) {
   return guard([&] { return M(p)->compress_device(code); }, (uint64_t)0);
 }
+void MR_set_device_args(void* p, int nargs, void** ptrs, const uint64_t* nbytes) {
+  guardv([&] {
+    if (nargs < 0 || (nargs > 0 && (!ptrs || !nbytes))) throw std::runtime_error("MR_set_device_args: bad arguments");
+    const at::Device dev = M(p)->device();
+    const auto o = at::TensorOptions().device(dev).dtype(at::kByte);
+    std::vector<at::Tensor> bufs;
+    for (int i = 0; i < nargs; ++i) {
+      // the caller's memory, wrapped without taking ownership
+      if (ptrs[i] && nbytes[i]) bufs.push_back(at::from_blob(ptrs[i], {(int64_t)nbytes[i]}, [](void*) {}, o, dev));
+      else bufs.push_back(at::empty({0}, o));
+    }
+    M(p)->set_device_args(std::move(bufs));
+  });
+}
+uint64_t MR_scan_device(void* p, const char* code) {
+  return guard([&] { return M(p)->scan_device(code); }, (uint64_t)0);
+}
 uint64_t MR_sort_keys_device(void* p, const char* code, int bits) {
   return guard([&] { return M(p)->sort_keys_device(code, bits); }, (uint64_t)0);
 }

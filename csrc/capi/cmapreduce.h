@@ -92,6 +92,14 @@ uint64_t MR_sort_keys_device(void *MRptr, const char *code, int bits);
 uint64_t MR_sort_values_device(void *MRptr, const char *code, int bits);
 /* the values of every key of a KMV, sorted by either functor; returns the global key count */
 uint64_t MR_sort_multivalues_device(void *MRptr, const char *code, int bits);
+/* the functors' user argument (MR-MPI's ptr): nargs (<= 8) raw device buffers, device_ptrs[i] of
+   nbytes[i] bytes, which every later *_device call hands to its functors as mrd::Args (an optional
+   trailing `const mrd::Args&` of every entry point). The caller keeps the buffers alive while they are
+   bound and ready on the stream the calls run on; they are wrapped, not owned. nargs 0 clears. */
+void MR_set_device_args(void *MRptr, int nargs, void **device_ptrs, const uint64_t *nbytes);
+/* read-only functor pass over the KV or KMV: mr_scan (devfn.h) runs once per pair / key and writes
+   to the bound buffers (mrd::MutArgs); returns the global pair / key count */
+uint64_t MR_scan_device(void *MRptr, const char *code);
 uint64_t MR_multivalue_blocks(void *MRptr, int *nblock);
 void MR_multivalue_block_select(void *MRptr, int which);
 int MR_multivalue_block(void *MRptr, int iblock, char **ptr_multivalue, int **ptr_valuesizes);

@@ -508,6 +508,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("sort_multivalues_device", &MR::sort_multivalues_device, py::arg("code"), py::arg("bits") = 64,
            py::call_guard<py::gil_scoped_release>())
+      .def("scan_device", &MR::scan_device, py::arg("code"), py::call_guard<py::gil_scoped_release>())
+      // None stands for an undefined tensor (rejected with its index, like every other bad entry)
+      .def("set_device_args",
+           [](MR& r, const std::vector<c10::optional<at::Tensor>>& bufs) {
+             std::vector<at::Tensor> v;
+             for (const auto& b : bufs) v.push_back(b ? *b : at::Tensor());
+             r.set_device_args(std::move(v));
+           })
+      .def("device_args", [](const MR& r) { return r.device_args(); })
       .def("compress_batch",
            [](MR& r, py::function fn) {
              py::gil_scoped_release nogil;
@@ -975,6 +984,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("device_compare_check", &devfn::compile_check_compare, py::arg("code"),
         py::call_guard<py::gil_scoped_release>());
   m.def("device_compare_tile", &devfn::compare_tile);
+  m.def("device_scan_check", &devfn::compile_check_scan, py::arg("code"), py::arg("kmv"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("device_functor_compiles", &devfn::compile_count);
   m.def("host_arena_reserve", &hostarena::reserve, py::call_guard<py::gil_scoped_release>());
   m.def("host_arena_stats", [] {
     hostarena::Stats s = hostarena::stats();

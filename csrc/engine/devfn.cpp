@@ -11,13 +11,16 @@
 // into a fixed-width KV, so later ops keep their fixed-key fast paths.
 // The two sort functors have kernels of their own: mrd_sortkey (a 64-bit key
 // per row for the radix sort) and the comparator merge sort (kCompareKernels).
-// Modules are cached per (device, kind, code).
+// mr_scan (kind 5) has mrd_scan: one pass, once per item, nothing emitted.
+// Every kernel that runs user code takes the bound buffers (devfn.h Args) as
+// its last argument, by value. Modules are cached per (device, kind, code).
 #include "devfn.h"
 
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
@@ -106,6 +109,36 @@ struct Emit {
   template <class K>
   __device__ void emit_key(const K& k) { emit(&k, sizeof(K), nullptr, 0); }
 };
+// a device buffer bound to the MapReduce object (set_device_args): p[0 .. n)
+// bytes, read-only to every functor but mr_scan
+struct Arg {
+  const u8* p;
+  i64 n;
+  template <class T>
+  __device__ const T* as() const { return reinterpret_cast<const T*>(p); }
+  template <class T>
+  __device__ i64 count() const { return n / (i64)sizeof(T); }
+};
+// the bound buffers, one by-value kernel argument; args[i] past n is {nullptr, 0}
+struct Args {
+  Arg a[8];
+  int n;
+  __device__ Arg operator[](int i) const { return i >= 0 && i < n ? a[i] : Arg{nullptr, 0}; }
+};
+// the same for mr_scan, the one functor that runs once per item and may write
+struct MutArg {
+  u8* p;
+  i64 n;
+  template <class T>
+  __device__ T* as() const { return reinterpret_cast<T*>(p); }
+  template <class T>
+  __device__ i64 count() const { return n / (i64)sizeof(T); }
+};
+struct MutArgs {
+  MutArg a[8];
+  int n;
+  __device__ MutArg operator[](int i) const { return i >= 0 && i < n ? a[i] : MutArg{nullptr, 0}; }
+};
 }  // namespace mrd
 // ---- user code ----
 )MRD";
@@ -127,30 +160,76 @@ __device__ inline i64 seg_of(const i64* seg, i64 nseg, i64 j) {
   }
   return lo;
 }
+// Every entry point may take a trailing `const mrd::Args&`, each on its own.
+// Of each pair of call shims the first (tag int, preferred for the literal 0)
+// is viable when the user's function takes the bound buffers, the second (tag
+// long) when it does not. Both are templates whose call is dependent, so the
+// form the user did not write is a substitution failure, not an error.
+#if MRD_REDUCE == 2
+template <class A>
+__device__ auto call_init(Bytes k, A& a, const Args& g, int) -> decltype(mr_init(k, a, g), void()) { mr_init(k, a, g); }
+template <class A>
+__device__ auto call_init(Bytes k, A& a, const Args&, long) -> decltype(mr_init(k, a), void()) { mr_init(k, a); }
+template <class A>
+__device__ auto call_add(A& a, Bytes v, const Args& g, int) -> decltype(mr_add(a, v, g), void()) { mr_add(a, v, g); }
+template <class A>
+__device__ auto call_add(A& a, Bytes v, const Args&, long) -> decltype(mr_add(a, v), void()) { mr_add(a, v); }
+template <class A>
+__device__ auto call_merge(A& a, const A& b, const Args& g, int) -> decltype(mr_merge(a, b, g), void()) { mr_merge(a, b, g); }
+template <class A>
+__device__ auto call_merge(A& a, const A& b, const Args&, long) -> decltype(mr_merge(a, b), void()) { mr_merge(a, b); }
+template <class A, class E>
+__device__ auto call_finish(Bytes k, const A& a, E& e, const Args& g, int) -> decltype(mr_finish(k, a, e, g), void()) {
+  mr_finish(k, a, e, g);
+}
+template <class A, class E>
+__device__ auto call_finish(Bytes k, const A& a, E& e, const Args&, long) -> decltype(mr_finish(k, a, e), void()) {
+  mr_finish(k, a, e);
+}
+#elif MRD_REDUCE
+template <class E>
+__device__ auto call_reduce(Bytes k, Values v, E& e, const Args& g, int) -> decltype(mr_reduce(k, v, e, g), void()) {
+  mr_reduce(k, v, e, g);
+}
+template <class E>
+__device__ auto call_reduce(Bytes k, Values v, E& e, const Args&, long) -> decltype(mr_reduce(k, v, e), void()) {
+  mr_reduce(k, v, e);
+}
+#else
+template <class E>
+__device__ auto call_map(Bytes k, Bytes v, i64 t, E& e, const Args& g, int) -> decltype(mr_map(k, v, t, e, g), void()) {
+  mr_map(k, v, t, e, g);
+}
+template <class E>
+__device__ auto call_map(Bytes k, Bytes v, i64 t, E& e, const Args&, long) -> decltype(mr_map(k, v, t, e), void()) {
+  mr_map(k, v, t, e);
+}
+#endif
 __device__ inline void run_item(const u8* kd, const i64* koff, i64 kw, const u8* vd, const i64* voff, i64 vw,
-                                const i64* seg, i64 first, i64 i, Emit& e) {
+                                const i64* seg, i64 first, i64 i, Emit& e, const Args& g) {
 #if MRD_REDUCE == 2
   // fold: vd = the merged accumulators, voff = each key's first chunk, vw = sizeof(mr_acc)
   mr_acc a;
   __builtin_memcpy(&a, vd + voff[i] * vw, sizeof(mr_acc));
-  mr_finish(field(kd, koff, kw, i), a, e);
+  call_finish(field(kd, koff, kw, i), a, e, g, 0);
 #elif MRD_REDUCE
   Values vals{vd + 0, voff, vw, seg[i + 1] - seg[i]};
   if (voff) vals.off = voff + seg[i];
   else vals.d = vd + seg[i] * vw;
-  mr_reduce(field(kd, koff, kw, i), vals, e);
+  call_reduce(field(kd, koff, kw, i), vals, e, g, 0);
 #else
-  mr_map(field(kd, koff, kw, first + i), field(vd, voff, vw, first + i), first + i, e);
+  call_map(field(kd, koff, kw, first + i), field(vd, voff, vw, first + i), first + i, e, g, 0);
 #endif
 }
 }  // namespace mrd
 extern "C" __global__ __launch_bounds__(256) void
 mrd_count(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff,
-          mrd::i64 vw, const mrd::i64* seg, mrd::i64 first, mrd::i64 n, mrd::i64* cnt, mrd::u64* wid, int bytes) {
+          mrd::i64 vw, const mrd::i64* seg, mrd::i64 first, mrd::i64 n, mrd::i64* cnt, mrd::u64* wid, int bytes,
+          mrd::Args args) {
   mrd::u64 kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0;
   for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
     mrd::Emit e{false, 0, 0, 0, ~0ull, 0, ~0ull, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
-    mrd::run_item(kd, koff, kw, vd, voff, vw, seg, first, i, e);
+    mrd::run_item(kd, koff, kw, vd, voff, vw, seg, first, i, e, args);
     cnt[i] = e.nrec;
     if (bytes) {  // the byte columns only when the widths turned out not uniform (a second count pass)
       cnt[n + i] = e.kb;
@@ -214,14 +293,14 @@ mrd_fold_nchunks(const mrd::i64* seg, mrd::i64 nkey, mrd::i64 C, mrd::i64* cnt, 
 extern "C" __global__ __launch_bounds__(256) void
 mrd_fold_chunks(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff,
                 mrd::i64 vw, const mrd::i64* seg, mrd::i64 nkey, const mrd::i64* cstart, mrd::i64 nchunk,
-                mrd::i64 C, mrd::u8* accs) {
+                mrd::i64 C, mrd::u8* accs, mrd::Args args) {
   for (mrd::i64 c = (mrd::i64)blockIdx.x * 256 + threadIdx.x; c < nchunk; c += (mrd::i64)gridDim.x * 256) {
     const mrd::i64 s = mrd::seg_of(cstart, nkey, c);
     const mrd::i64 a0 = seg[s] + (c - cstart[s]) * C;
     const mrd::i64 a1 = a0 + C < seg[s + 1] ? a0 + C : seg[s + 1];
     mr_acc a;
-    mr_init(mrd::field(kd, koff, kw, s), a);
-    for (mrd::i64 v = a0; v < a1; ++v) mr_add(a, mrd::field(vd, voff, vw, v));
+    mrd::call_init(mrd::field(kd, koff, kw, s), a, args, 0);
+    for (mrd::i64 v = a0; v < a1; ++v) mrd::call_add(a, mrd::field(vd, voff, vw, v), args, 0);
     __builtin_memcpy(accs + c * sizeof(mr_acc), &a, sizeof(mr_acc));
   }
 }
@@ -229,7 +308,8 @@ mrd_fold_chunks(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd:
 // takes in chunk j + stride; log2(most chunks of a key) levels leave each
 // key's total in its first chunk, in the same order on every run
 extern "C" __global__ __launch_bounds__(256) void
-mrd_fold_merge(const mrd::i64* cstart, mrd::i64 nkey, mrd::i64 nchunk, mrd::i64 stride, mrd::u8* accs) {
+mrd_fold_merge(const mrd::i64* cstart, mrd::i64 nkey, mrd::i64 nchunk, mrd::i64 stride, mrd::u8* accs,
+               mrd::Args args) {
   for (mrd::i64 c = (mrd::i64)blockIdx.x * 256 + threadIdx.x; c < nchunk; c += (mrd::i64)gridDim.x * 256) {
     const mrd::i64 s = mrd::seg_of(cstart, nkey, c);
     const mrd::i64 j = c - cstart[s];
@@ -237,7 +317,7 @@ mrd_fold_merge(const mrd::i64* cstart, mrd::i64 nkey, mrd::i64 nchunk, mrd::i64 
     mr_acc a, b;
     __builtin_memcpy(&a, accs + c * sizeof(mr_acc), sizeof(mr_acc));
     __builtin_memcpy(&b, accs + (c + stride) * sizeof(mr_acc), sizeof(mr_acc));
-    mr_merge(a, b);
+    mrd::call_merge(a, b, args, 0);
     __builtin_memcpy(accs + c * sizeof(mr_acc), &a, sizeof(mr_acc));
   }
 }
@@ -248,7 +328,7 @@ extern "C" __global__ __launch_bounds__(256) void
 mrd_write(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff,
           mrd::i64 vw, const mrd::i64* seg, mrd::i64 first, mrd::i64 n, const mrd::i64* pr, const mrd::i64* pk,
           const mrd::i64* pv, mrd::i64 okw, mrd::i64 ovw, mrd::u8* okd, mrd::i64* okoff, mrd::u8* ovd,
-          mrd::i64* ovoff) {
+          mrd::i64* ovoff, mrd::Args args) {
   // pr / pk / pv: exclusive scans (n + 1) of records, key bytes, value bytes
   // (pk / pv unused when that width is uniform: okw / ovw >= 0)
   for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
@@ -259,7 +339,7 @@ mrd_write(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* v
     const mrd::i64 k1 = okw >= 0 ? r1 * okw : pk[i + 1], v1 = ovw >= 0 ? r1 * ovw : pv[i + 1];
     mrd::Emit e{true, 0, 0, 0, 0, 0, 0, 0, okd + k0, okw >= 0 ? nullptr : okoff + r, ovd + v0,
                 ovw >= 0 ? nullptr : ovoff + r, r1 - r, k1 - k0, v1 - v0};
-    mrd::run_item(kd, koff, kw, vd, voff, vw, seg, first, i, e);
+    mrd::run_item(kd, koff, kw, vd, voff, vw, seg, first, i, e, args);
     const mrd::i64 nw = e.nrec < r1 - r ? e.nrec : r1 - r;
     for (mrd::i64 j = 0; j < nw; ++j) {  // offsets relative to the item -> absolute
       if (okw < 0) okoff[r + j] += k0;
@@ -272,11 +352,19 @@ mrd_write(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* v
 // kind 3: a sort-key functor, __device__ unsigned long long mr_sortkey(mrd::Bytes)
 const char* kSortKernel = R"MRD(
 // ---- mrd sort-key kernel ----
+namespace mrd {
+// mr_sortkey with or without the trailing `const mrd::Args&` (the call shims of the map / reduce kernels)
+template <class B>
+__device__ auto call_sortkey(B b, const Args& g, int) -> decltype(mr_sortkey(b, g)) { return mr_sortkey(b, g); }
+template <class B>
+__device__ auto call_sortkey(B b, const Args&, long) -> decltype(mr_sortkey(b)) { return mr_sortkey(b); }
+}  // namespace mrd
 extern "C" __global__ __launch_bounds__(256) void
-mrd_sortkey(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, mrd::u64* key, unsigned int* idx) {
+mrd_sortkey(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, mrd::u64* key, unsigned int* idx,
+            mrd::Args args) {
   for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
     const mrd::Bytes b = off ? mrd::Bytes{d + off[i], off[i + 1] - off[i]} : mrd::Bytes{d + i * w, w};
-    key[i] = mr_sortkey(b);
+    key[i] = mrd::call_sortkey(b, args, 0);
     idx[i] = (unsigned int)i;
   }
 }
@@ -311,18 +399,24 @@ const char* kCompareKernels = R"MRD(
 namespace mrd {
 typedef unsigned int u32;
 enum { CMP_T = MRD_CMP_T, CMP_PER = MRD_CMP_T / 256 };
+// mr_compare with or without the trailing `const mrd::Args&` (the call shims of the map / reduce kernels)
+template <class B>
+__device__ auto call_compare(B a, B b, const Args& g, int) -> decltype(mr_compare(a, b, g)) { return mr_compare(a, b, g); }
+template <class B>
+__device__ auto call_compare(B a, B b, const Args&, long) -> decltype(mr_compare(a, b)) { return mr_compare(a, b); }
 struct Cmp {
   const u8* d;
   const i64* off;
   i64 w;
   const i64* sid;  // segment id of every row, compared first (null: no segments)
+  const Args& g;   // the bound buffers (the kernel's own argument)
   __device__ Bytes row(u32 i) const { return off ? Bytes{d + off[i], off[i + 1] - off[i]} : Bytes{d + i * w, w}; }
   __device__ bool less(u32 i, u32 j) const {
     if (sid) {
       const i64 a = sid[i], b = sid[j];
       if (a != b) return a < b;
     }
-    const int c = mr_compare(row(i), row(j));
+    const int c = call_compare(row(i), row(j), g, 0);
     return c < 0 || (c == 0 && i < j);
   }
 };
@@ -369,11 +463,12 @@ __device__ inline void cmp_merge_tile(const Cmp& c, const u32* src, u32* dst, in
 }
 }  // namespace mrd
 extern "C" __global__ __launch_bounds__(256) void
-mrd_cmp_blocksort(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64* sid, mrd::i64 n, mrd::u32* out) {
+mrd_cmp_blocksort(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64* sid, mrd::i64 n, mrd::u32* out,
+                  mrd::Args args) {
   using namespace mrd;
   __shared__ u32 buf[2][CMP_T];
   __shared__ int split[257];
-  const Cmp c{d, off, w, sid};
+  const Cmp c{d, off, w, sid, args};
   const i64 base = (i64)blockIdx.x * CMP_T;
   const int cnt = n - base < CMP_T ? (int)(n - base) : CMP_T;
   const int t = threadIdx.x;
@@ -416,12 +511,12 @@ mrd_cmp_blocksort(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::
 }
 extern "C" __global__ __launch_bounds__(256) void
 mrd_cmp_merge(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64* sid, mrd::i64 n,
-              const mrd::u32* src, mrd::u32* dst, mrd::i64 W) {
+              const mrd::u32* src, mrd::u32* dst, mrd::i64 W, mrd::Args args) {
   using namespace mrd;
   __shared__ u32 buf[2][CMP_T];
   __shared__ int split[257];
   __shared__ i64 ends[2];
-  const Cmp c{d, off, w, sid};
+  const Cmp c{d, off, w, sid, args};
   const int t = threadIdx.x;
   const i64 g0 = (i64)blockIdx.x * CMP_T;  // this workgroup's output tile: dst[g0, g0 + cnt)
   const int cnt = n - g0 < CMP_T ? (int)(n - g0) : CMP_T;
@@ -449,6 +544,29 @@ mrd_cmp_merge(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, const mrd::i64*
 }
 )MRD";
 
+// kind 5: a scan functor, mr_scan in its KV (MRD_SCAN_KMV 0) or KMV (1) shape.
+// One thread per item, every item exactly once; nothing is emitted, the
+// functor writes to the bound buffers (mrd::MutArgs).
+const char* kScanKernel = R"MRD(
+// ---- mrd scan kernel ----
+extern "C" __global__ __launch_bounds__(256) void
+mrd_scan(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff, mrd::i64 vw,
+         const mrd::i64* seg, mrd::i64 base, mrd::i64 n, mrd::MutArgs args) {
+  for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
+    const mrd::Bytes key = koff ? mrd::Bytes{kd + koff[i], koff[i + 1] - koff[i]} : mrd::Bytes{kd + i * kw, kw};
+#if MRD_SCAN_KMV
+    mrd::Values vals{vd, voff, vw, seg[i + 1] - seg[i]};
+    if (voff) vals.off = voff + seg[i];
+    else vals.d = vd + seg[i] * vw;
+    mr_scan(key, vals, args);
+#else
+    const mrd::Bytes val = voff ? mrd::Bytes{vd + voff[i], voff[i + 1] - voff[i]} : mrd::Bytes{vd + i * vw, vw};
+    mr_scan(key, val, base + i, args);
+#endif
+  }
+}
+)MRD";
+
 struct Module {
   hipModule_t mod = nullptr;
   hipFunction_t count = nullptr, write = nullptr;
@@ -459,18 +577,30 @@ const char* kind_name(int kind) {
          : kind == 1 ? "mrd_reduce.hip"
          : kind == 2 ? "mrd_fold.hip"
          : kind == 3 ? "mrd_sortkey.hip"
-                     : "mrd_compare.hip";
+         : kind == 4 ? "mrd_compare.hip"
+                     : "mrd_scan.hip";
 }
 // rows per workgroup tile of the comparator sort (256 threads, 8 rows each)
 constexpr int64_t kCompareTile = 2048;
+// kind 5 (scan): code = scan_code(user code, kmv), the shape's define in front
+std::string scan_code(const std::string& code, bool kmv) {
+  return std::string("#define MRD_SCAN_KMV ") + (kmv ? "1\n" : "0\n") + code;
+}
 std::string source_of(const std::string& code, int kind) {
+  if (kind == 5) {  // the define goes before the prelude like the others'
+    const size_t nl = code.find('\n');
+    return code.substr(0, nl + 1) + kDevicePrelude + code.substr(nl + 1) + "\n" + kScanKernel;
+  }
   if (kind == 3) return std::string(kDevicePrelude) + code + "\n" + kSortKernel;
   if (kind == 4)
     return "#define MRD_CMP_T " + std::to_string(kCompareTile) + "\n" + kDevicePrelude + code + "\n" + kCompareKernels;
   return "#define MRD_REDUCE " + std::to_string(kind) + "\n" + kDevicePrelude + code + "\n" + kKernels;
 }
 
+std::atomic<int64_t> g_compiles{0};
+
 std::string compile(const std::string& src, const char* name) {
+  g_compiles++;
   hiprtcProgram p;
   if (hiprtcCreateProgram(&p, src.c_str(), name, 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     throw std::runtime_error("mrhip: hiprtcCreateProgram failed");
@@ -506,6 +636,14 @@ const Module& module_for(const std::string& code, int kind, int device) {
         hipModuleGetFunction(&m->count, m->mod, "mrd_sortkey") != hipSuccess) {
       (void)hipGetLastError();
       throw std::runtime_error("mrhip: loading the sort-key functor's code object failed");
+    }
+    return *cache.emplace(key, std::move(m)).first->second;
+  }
+  if (kind == 5) {
+    if (hipModuleLoadData(&m->mod, obj.data()) != hipSuccess ||
+        hipModuleGetFunction(&m->count, m->mod, "mrd_scan") != hipSuccess) {
+      (void)hipGetLastError();
+      throw std::runtime_error("mrhip: loading the scan functor's code object failed");
     }
     return *cache.emplace(key, std::move(m)).first->second;
   }
@@ -556,7 +694,7 @@ struct Items {
   int64_t first = 0, n = 0;
 };
 
-KV run(const Items& it, const std::string& code, int kind, at::Device dev) {
+KV run(const Items& it, const std::string& code, int kind, at::Device dev, const Args& bound) {
   if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
   KV out;
   out.kw = out.vw = -1;
@@ -583,7 +721,8 @@ KV run(const Items& it, const std::string& code, int kind, at::Device dev) {
     int64_t* c = P0<int64_t>(cnt);
     int64_t* w = P0<int64_t>(wid);
     int b = bytes;
-    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &first, &n, &c, &w, &b};
+    Args g = bound;
+    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &first, &n, &c, &w, &b, &g};
     launch(m.count, it.n, args, s);
   };
   count(0);
@@ -629,7 +768,9 @@ KV run(const Items& it, const std::string& code, int kind, at::Device dev) {
     uint8_t* ovd = P0<uint8_t>(out.vdata);
     int64_t* okoff = P0<int64_t>(out.koff);
     int64_t* ovoff = P0<int64_t>(out.voff);
-    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &first, &n, &ppr, &ppk, &ppv, &kwo, &vwo, &okd, &okoff, &ovd, &ovoff};
+    Args g = bound;
+    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw,  &seg, &first, &n,     &ppr,
+                    &ppk, &ppv, &kwo, &vwo, &okd, &okoff, &ovd, &ovoff, &g};
     launch(m.write, it.n, args, s);
   }
   if (out.koff.defined()) k::fill_i64(P0<int64_t>(out.koff) + nout, 1, tot[1], s);
@@ -649,7 +790,7 @@ int64_t compile_check_sortkey(const std::string& code) {
 }
 
 std::pair<at::Tensor, at::Tensor> sort_keys_of(const at::Tensor& data, const at::Tensor& off, int w, int64_t n,
-                                               const std::string& code, at::Device dev) {
+                                               const std::string& code, at::Device dev, const Args& bound) {
   if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
   at::Tensor key = at::empty({std::max<int64_t>(n, 1)}, opt(dev, at::kLong));
   at::Tensor idx = at::empty({std::max<int64_t>(n, 1)}, opt(dev, at::kInt));
@@ -660,7 +801,8 @@ std::pair<at::Tensor, at::Tensor> sort_keys_of(const at::Tensor& data, const at:
     int64_t ww = w >= 0 ? w : 0, nn = n;
     int64_t* k = P0<int64_t>(key);
     int32_t* ix = P0<int32_t>(idx);
-    void* args[] = {&d, &o, &ww, &nn, &k, &ix};
+    Args g = bound;
+    void* args[] = {&d, &o, &ww, &nn, &k, &ix, &g};
     launch(m.count, n, args, at::hip::getCurrentHIPStream());
   }
   return {key.narrow(0, 0, n), idx.narrow(0, 0, n)};
@@ -681,7 +823,7 @@ int64_t compile_check_compare(const std::string& code) {
 int64_t compare_tile() { return kCompareTile; }
 
 at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, int64_t n, const at::Tensor& sid,
-                        const std::string& code, at::Device dev) {
+                        const std::string& code, at::Device dev, const Args& bound) {
   if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
   if (n > (int64_t)UINT32_MAX)
     throw std::runtime_error("mrhip: the comparator sort indexes rows with 32 bits; " + std::to_string(n) +
@@ -699,6 +841,7 @@ at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, in
   int64_t ww = w >= 0 ? w : 0, nn = n;
   uint32_t* src = P0<uint32_t>(a);
   uint32_t* dst = P0<uint32_t>(b);
+  Args g = bound;
   auto go = [&](hipFunction_t f, void** args) {
     if (hipModuleLaunchKernel(f, tiles, 1, 1, 256, 1, 1, 0, s, args, nullptr) != hipSuccess) {
       (void)hipGetLastError();
@@ -706,12 +849,12 @@ at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, in
     }
   };
   {
-    void* args[] = {&d, &o, &ww, &sg, &nn, &src};
+    void* args[] = {&d, &o, &ww, &sg, &nn, &src, &g};
     go(m.count, args);
   }
   // ceil(log2(tiles)) passes, known from n alone: nothing is read back between them
   for (int64_t W = kCompareTile; W < n; W *= 2) {
-    void* args[] = {&d, &o, &ww, &sg, &nn, &src, &dst, &W};
+    void* args[] = {&d, &o, &ww, &sg, &nn, &src, &dst, &W, &g};
     go(m.write, args);
     std::swap(src, dst);
     std::swap(a, b);
@@ -723,7 +866,7 @@ int64_t compile_check(const std::string& code, bool reduce) {
   return (int64_t)compile(full_source(code, reduce), kind_name(kind_of(code, reduce))).size();
 }
 
-KV map_pairs(const KV& kv_in, const std::string& code, at::Device dev, int64_t a, int64_t b) {
+KV map_pairs(const KV& kv_in, const std::string& code, at::Device dev, int64_t a, int64_t b, const Args& bound) {
   KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
   if (b < 0 || b > kv.n) b = kv.n;
   Items it;
@@ -735,17 +878,17 @@ KV map_pairs(const KV& kv_in, const std::string& code, at::Device dev, int64_t a
   it.voff = kv.vfixed() ? nullptr : P0<int64_t>(kv.voff);
   it.vw = kv.vfixed() ? kv.vw : 0;
   it.n = std::max<int64_t>(0, b - a);
-  return run(it, code, 0, dev);
+  return run(it, code, 0, dev, bound);
 }
 
-KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev) {
+KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev, const Args& bound) {
   Items it;
   it.first = first;
   it.n = n;
-  return run(it, code, 0, dev);
+  return run(it, code, 0, dev, bound);
 }
 
-KV reduce_groups(const KMV& m, const std::string& code, at::Device dev) {
+KV reduce_groups(const KMV& m, const std::string& code, at::Device dev, const Args& bound) {
   if (m.nkey && !m.seg.is_cuda()) throw std::runtime_error("mrhip: reduce_device needs the groups in HBM");
   Items it;
   const KV& k = m.keys;
@@ -757,9 +900,9 @@ KV reduce_groups(const KMV& m, const std::string& code, at::Device dev) {
   it.vw = m.vw >= 0 ? m.vw : 0;
   it.seg = P0<int64_t>(m.seg);
   it.n = m.nkey;
-  if (kind_of(code, true) == 1) return run(it, code, 1, dev);
+  if (kind_of(code, true) == 1) return run(it, code, 1, dev, bound);
   // fold tier: accumulators per chunk of values, merged per key, then mr_finish per key
-  if (!it.n) return run(it, code, 2, dev);
+  if (!it.n) return run(it, code, 2, dev, bound);
   const Module& mod = module_for(code, 2, dev.index());
   hipStream_t s = at::hip::getCurrentHIPStream();
   static const int64_t C = [] {
@@ -797,11 +940,12 @@ KV reduce_groups(const KMV& m, const std::string& code, at::Device dev) {
     const int64_t* seg = it.seg;
     const int64_t* cs = P0<int64_t>(cstart);
     uint8_t* a = P0<uint8_t>(accs);
-    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &nkey, &cs, &nc, &c, &a};
+    Args g = bound;
+    void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &nkey, &cs, &nc, &c, &a, &g};
     launch(mod.chunks, nchunk, args, s);
     for (int64_t stride = 1; stride < maxc; stride *= 2) {
       int64_t st = stride;
-      void* margs[] = {&cs, &nkey, &nc, &st, &a};
+      void* margs[] = {&cs, &nkey, &nc, &st, &a, &g};
       launch(mod.merge, nchunk, margs, s);
     }
   }
@@ -810,7 +954,72 @@ KV reduce_groups(const KMV& m, const std::string& code, at::Device dev) {
   f.voff = P0<int64_t>(cstart);
   f.vw = asz;
   f.seg = nullptr;
-  return run(f, code, 2, dev);
+  return run(f, code, 2, dev, bound);
+}
+
+Args args_of(const std::vector<at::Tensor>& bufs) {
+  if ((int)bufs.size() > kMaxArgs)
+    throw std::runtime_error("mrhip: a device functor takes at most 8 bound buffers, " + std::to_string(bufs.size()) +
+                             " given");
+  Args g{};
+  g.n = (int)bufs.size();
+  for (int i = 0; i < g.n; ++i) g.a[i] = {bufs[i].numel() ? bufs[i].data_ptr() : nullptr, (int64_t)bufs[i].nbytes()};
+  return g;
+}
+
+int64_t compile_count() { return g_compiles.load(); }
+
+int64_t compile_check_scan(const std::string& code, bool kmv) {
+  return (int64_t)compile(source_of(scan_code(code, kmv), 5), kind_name(5)).size();
+}
+
+namespace {
+int64_t run_scan(const Items& it, const std::string& code, bool kmv, at::Device dev, const Args& bound) {
+  if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  if (it.n <= 0) return 0;
+  const Module& m = module_for(scan_code(code, kmv), 5, dev.index());
+  const uint8_t* kd = it.kd;
+  const int64_t* koff = it.koff;
+  int64_t kw = it.kw, vw = it.vw, base = it.first, n = it.n;
+  const uint8_t* vd = it.vd;
+  const int64_t* voff = it.voff;
+  const int64_t* seg = it.seg;
+  Args g = bound;
+  void* args[] = {&kd, &koff, &kw, &vd, &voff, &vw, &seg, &base, &n, &g};
+  launch(m.count, it.n, args, at::hip::getCurrentHIPStream());
+  return it.n;
+}
+}  // namespace
+
+int64_t scan_pairs(const KV& kv_in, int64_t base, const std::string& code, at::Device dev, const Args& bound) {
+  if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
+  Items it;
+  it.first = base;
+  it.kd = P0<uint8_t>(kv.kdata);
+  it.koff = kv.kfixed() ? nullptr : P0<int64_t>(kv.koff);
+  it.kw = kv.kfixed() ? kv.kw : 0;
+  it.vd = P0<uint8_t>(kv.vdata);
+  it.voff = kv.vfixed() ? nullptr : P0<int64_t>(kv.voff);
+  it.vw = kv.vfixed() ? kv.vw : 0;
+  it.n = kv.n;
+  return run_scan(it, code, false, dev, bound);
+}
+
+int64_t scan_groups(const KMV& m, const std::string& code, at::Device dev, const Args& bound) {
+  if (!dev.is_cuda()) throw std::runtime_error("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  if (m.nkey && !m.seg.is_cuda()) throw std::runtime_error("mrhip: scan_device needs the groups in HBM");
+  Items it;
+  const KV& k = m.keys;
+  it.kd = P0<uint8_t>(k.kdata);
+  it.koff = k.kfixed() ? nullptr : P0<int64_t>(k.koff);
+  it.kw = k.kfixed() ? k.kw : 0;
+  it.vd = P0<uint8_t>(m.vdata);
+  it.voff = m.vw >= 0 ? nullptr : P0<int64_t>(m.voff);
+  it.vw = m.vw >= 0 ? m.vw : 0;
+  it.seg = P0<int64_t>(m.seg);
+  it.n = m.nkey;
+  return run_scan(it, code, true, dev, bound);
 }
 
 }  // namespace devfn

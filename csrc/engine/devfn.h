@@ -13,21 +13,62 @@
 // trivially copyable k, v. It must be a pure function of its arguments (it
 // runs twice: count, then write). The prelude (kDevicePrelude in devfn.cpp)
 // documents mrd::Bytes / mrd::Values / mrd::Emit.
+//
+// The user argument (MR-MPI's `ptr`): up to kMaxArgs device buffers bound to
+// the MapReduce object (set_device_args) reach every functor kernel as ONE
+// by-value kernel argument, a struct of 8 x {pointer, byte count} and a count
+// (Args below = mrd::Args in the prelude). No global symbol in the module, no
+// allocation, nothing shared between two ops that run one cached module; the
+// module cache key stays (device, kind, code), so new contents or new buffers
+// never recompile. Every entry point (mr_map, mr_reduce, mr_init, mr_add,
+// mr_merge, mr_finish, mr_sortkey, mr_compare) MAY take one trailing
+// `const mrd::Args& args` parameter, each function on its own; args[i] is
+// {p, n bytes} ({nullptr, 0} past the bound count), args[i].as<T>() a
+// `const T*`, args[i].count<T>() the number of T. These functors run more than
+// once per item (count, write) or in an unspecified order (fold, sorts): the
+// buffers are read-only to them, and the purity rule now reads "a pure
+// function of its arguments and the bound buffers' contents".
+//
+// scan (kind 5) is the one functor that writes to the bound buffers:
+//   __device__ void mr_scan(mrd::Bytes key, mrd::Bytes value, long long index, const mrd::MutArgs& args);  // KV
+//   __device__ void mr_scan(mrd::Bytes key, mrd::Values values, const mrd::MutArgs& args);                 // KMV
+// runs exactly once per item (one thread each) and emits nothing; it writes
+// through args[i].as<T>() (a `T*`) with atomics or plain stores to distinct
+// slots. The engine orders nothing beyond the stream.
+//
+// Lifetime and streams: the caller of the functions below keeps the buffers
+// alive (the MapReduce object holds the bound tensors); the kernels run on the
+// current stream and the buffers must be ready on it.
 #pragma once
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "kv.h"
 
 namespace mrh {
 namespace devfn {
+// the bound buffers as every functor kernel takes them (layout of mrd::Args /
+// mrd::MutArgs in the prelude); slots past n are {nullptr, 0}
+constexpr int kMaxArgs = 8;
+struct Args {
+  struct Buf {
+    const void* p;
+    int64_t n;  // bytes
+  } a[kMaxArgs];
+  int n;
+};
+// of tensors that are defined, contiguous and on one device (the caller's
+// check: MapReduce::set_device_args); at most kMaxArgs
+Args args_of(const std::vector<at::Tensor>& bufs);
 // map: pairs [a, b) of kv (b < 0: to the end; on the GPU) through mr_map;
 // index = the pair's index in kv
-KV map_pairs(const KV& kv, const std::string& code, at::Device dev, int64_t a = 0, int64_t b = -1);
+KV map_pairs(const KV& kv, const std::string& code, at::Device dev, int64_t a = 0, int64_t b = -1,
+             const Args& args = Args{});
 // map over n tasks (no input): mr_map(empty, empty, task, out)
-KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev);
+KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev, const Args& args = Args{});
 // reduce: every key of m through mr_reduce
-KV reduce_groups(const KMV& m, const std::string& code, at::Device dev);
+KV reduce_groups(const KMV& m, const std::string& code, at::Device dev, const Args& args = Args{});
 // compile only (syntax / type errors come back with the compiler log);
 // returns the code object size in bytes. Works without a GPU.
 int64_t compile_check(const std::string& code, bool reduce);
@@ -36,7 +77,7 @@ int64_t compile_check(const std::string& code, bool reduce);
 // order (a comparator expressed as a key extraction); returns (keys [n],
 // row index [n] int32) for the engine's stable radix sort
 std::pair<at::Tensor, at::Tensor> sort_keys_of(const at::Tensor& data, const at::Tensor& off, int w, int64_t n,
-                                               const std::string& code, at::Device dev);
+                                               const std::string& code, at::Device dev, const Args& args = Args{});
 int64_t compile_check_sortkey(const std::string& code);
 // comparator functor: `__device__ int mr_compare(mrd::Bytes a, mrd::Bytes b)`
 // with MR-MPI's contract (< 0 a before b, 0 equal, > 0 b before a), a strict
@@ -46,7 +87,7 @@ int64_t compile_check_sortkey(const std::string& code);
 // (int64 [n], may be undefined) is compared before mr_compare: rows grouped
 // by segment are sorted inside every segment by one call.
 at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, int64_t n, const at::Tensor& sid,
-                        const std::string& code, at::Device dev);
+                        const std::string& code, at::Device dev, const Args& args = Args{});
 // compile only; the code object size in bytes. Works without a GPU.
 int64_t compile_check_compare(const std::string& code);
 // rows per workgroup tile of the comparator sort (a power of two)
@@ -54,6 +95,14 @@ int64_t compare_tile();
 // which sort functor the code defines: 3 = mr_sortkey (wins when both names
 // appear), 4 = mr_compare; neither is an error that names both
 int sort_kind_of(const std::string& code);
+// scan functor (mr_scan, see above) over the pairs of kv (on the GPU; index =
+// base + the pair's position in kv) / over every key of m; returns the items visited
+int64_t scan_pairs(const KV& kv, int64_t base, const std::string& code, at::Device dev, const Args& args);
+int64_t scan_groups(const KMV& m, const std::string& code, at::Device dev, const Args& args);
+// compile only (kmv: the KMV shape of mr_scan); the code object size in bytes
+int64_t compile_check_scan(const std::string& code, bool kmv);
+// hiprtc compilations this process has done so far (checks and module loads alike)
+int64_t compile_count();
 // the full source handed to the compiler (prelude + code + kernels)
 std::string full_source(const std::string& code, bool reduce);
 }  // namespace devfn

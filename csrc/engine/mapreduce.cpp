@@ -1380,8 +1380,26 @@ int64_t functor_chunk(const KeyValue& out, int64_t n) {
 }
 }  // namespace
 
+void MapReduce::set_device_args(std::vector<at::Tensor> bufs) {
+  if ((int)bufs.size() > devfn::kMaxArgs)
+    fail("mrhip: set_device_args: at most " + std::to_string(devfn::kMaxArgs) + " device buffers can be bound, " +
+         std::to_string(bufs.size()) + " given (argument " + std::to_string(devfn::kMaxArgs) + " is one too many)");
+  const at::Device dev = device();
+  for (size_t i = 0; i < bufs.size(); ++i) {
+    const std::string which = "mrhip: set_device_args: argument " + std::to_string(i);
+    const at::Tensor& t = bufs[i];
+    if (!t.defined()) fail(which + " is not a defined tensor");
+    if (!t.is_contiguous()) fail(which + " is not contiguous");
+    const bool same = t.device().type() == dev.type() &&
+                      (!dev.is_cuda() || !dev.has_index() || t.device().index() == dev.index());
+    if (!same) fail(which + " is on " + t.device().str() + ", this MapReduce's device is " + dev.str());
+  }
+  dev_args_ = std::move(bufs);
+}
+
 uint64_t MapReduce::map_device(MapReduce& src, const std::string& code, int addflag) {
   const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
   return map_mr_batch(
       src,
       [&](const KV& kv, KeyValue& out) {
@@ -1389,7 +1407,7 @@ uint64_t MapReduce::map_device(MapReduce& src, const std::string& code, int addf
         const KV d = kv.device() == dev ? kv : kv_to(kv, dev);
         const int64_t step = functor_chunk(out, d.n);
         for (int64_t a = 0; a < d.n; a += step) {
-          KV o = devfn::map_pairs(d, code, dev, a, std::min(d.n, a + step));
+          KV o = devfn::map_pairs(d, code, dev, a, std::min(d.n, a + step), bound);
           if (o.n) out.add_kv(o);
         }
       },
@@ -1401,13 +1419,14 @@ uint64_t MapReduce::map_device_tasks(int64_t ntask, const std::string& code, int
   // [t * ntask / P, (t + 1) * ntask / P) in one launch (any mapstyle)
   const int64_t P = comm_->size();
   const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
   return map(
       (int)P,
       [&](int t, KeyValue& out) {
         const int64_t a = (int64_t)t * ntask / P, b = (int64_t)(t + 1) * ntask / P;
         const int64_t step = functor_chunk(out, b - a);
         for (int64_t x = a; x < b; x += step) {
-          KV o = devfn::map_tasks(x, std::min(b, x + step) - x, code, dev);
+          KV o = devfn::map_tasks(x, std::min(b, x + step) - x, code, dev, bound);
           if (o.n) out.add_kv(o);
         }
       },
@@ -1416,9 +1435,10 @@ uint64_t MapReduce::map_device_tasks(int64_t ntask, const std::string& code, int
 
 uint64_t MapReduce::reduce_device(const std::string& code) {
   const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
   return reduce_batch([&](const KMV& m, KeyValue& out) {
     if (!m.nkey) return;
-    KV o = devfn::reduce_groups(m, code, dev);
+    KV o = devfn::reduce_groups(m, code, dev, bound);
     if (o.n) out.add_kv(o);
   });
 }
@@ -1426,15 +1446,16 @@ uint64_t MapReduce::reduce_device(const std::string& code) {
 namespace {
 // the pairs sorted by a device sort functor over one column, stable:
 // mr_sortkey -> radix sort of its 64-bit keys; mr_compare -> the merge sort
-KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_value, at::Device dev) {
+KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_value, at::Device dev,
+                   const devfn::Args& bound) {
   const int kind = devfn::sort_kind_of(code);
   if (kv_in.n <= 1) return kv_in;
   const KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
   const at::Tensor& data = by_value ? kv.vdata : kv.kdata;
   const at::Tensor& off = by_value ? kv.voff : kv.koff;
   const int w = by_value ? kv.vw : kv.kw;
-  if (kind == 4) return gather(kv, devfn::compare_perm(data, off, w, kv.n, at::Tensor(), code, dev));
-  auto [key, idx] = devfn::sort_keys_of(data, off, w, kv.n, code, dev);
+  if (kind == 4) return gather(kv, devfn::compare_perm(data, off, w, kv.n, at::Tensor(), code, dev, bound));
+  auto [key, idx] = devfn::sort_keys_of(data, off, w, kv.n, code, dev, bound);
   auto [ks, perm, passes] = radix_sort_pairs(key, idx, 0, std::max(1, std::min(bits, 64)));
   (void)ks;
   (void)passes;
@@ -1447,7 +1468,7 @@ uint64_t MapReduce::sort_keys_device(const std::string& code, int bits) {
   OpTrace tr_(__func__, this);
   enter(__func__);
   need_kv("sort_keys");
-  kv = sort_by_functor(*kv, code, bits, false, device());
+  kv = sort_by_functor(*kv, code, bits, false, device(), devfn::args_of(dev_args_));
   stats("Sort_keys", 0);
   return count(kv->n);
 }
@@ -1457,7 +1478,7 @@ uint64_t MapReduce::sort_values_device(const std::string& code, int bits) {
   OpTrace tr_(__func__, this);
   enter(__func__);
   need_kv("sort_values");
-  kv = sort_by_functor(*kv, code, bits, true, device());
+  kv = sort_by_functor(*kv, code, bits, true, device(), devfn::args_of(dev_args_));
   stats("Sort_values", 0);
   return count(kv->n);
 }
@@ -1469,6 +1490,7 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
   need_kmv("sort_multivalues");
   const int kind = devfn::sort_kind_of(code);
   const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
   if (kmv->nval > 1) {
     KMV m = *kmv;
     if (m.seg.device() != dev) {
@@ -1480,10 +1502,11 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
     at::Tensor perm;
     if (kind == 4) {
       // the values are grouped by key already: one sort under (segment id, mr_compare)
-      perm = devfn::compare_perm(m.vdata, m.voff, m.vw, m.nval, segment_ids(m.seg, m.nkey, m.nval), code, dev);
+      perm = devfn::compare_perm(m.vdata, m.voff, m.vw, m.nval, segment_ids(m.seg, m.nkey, m.nval), code, dev,
+                                 bound);
     } else {
       // LSD, as mrh::sort_multivalues: stable by the functor's key, then stable by segment id
-      auto [key, idx] = devfn::sort_keys_of(m.vdata, m.voff, m.vw, m.nval, code, dev);
+      auto [key, idx] = devfn::sort_keys_of(m.vdata, m.voff, m.vw, m.nval, code, dev, bound);
       auto [ks, perm1, p1] = radix_sort_pairs(key, idx, 0, std::max(1, std::min(bits, 64)));
       at::Tensor sid_p = segment_ids(m.seg, m.nkey, m.nval).index_select(0, perm1.to(at::kLong));
       auto [ss, perm2, p2] = radix_sort_pairs(sid_p, perm1, 0, 64);
@@ -1504,11 +1527,53 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
 
 uint64_t MapReduce::compress_device(const std::string& code) {
   const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
   return compress_batch([&](const KMV& m, KeyValue& out) {
     if (!m.nkey) return;
-    KV o = devfn::reduce_groups(m, code, dev);
+    KV o = devfn::reduce_groups(m, code, dev, bound);
     if (o.n) out.add_kv(o);
   });
+}
+
+// scan with a device functor: the data stays where and as it is. Pairs /
+// groups in HBM take one launch; host-resident data (past the HBM budget)
+// goes through HBM in budget-sized pieces, every item once, a pair's index
+// its index on this rank.
+uint64_t MapReduce::scan_device(const std::string& code) {
+  start();
+  OpTrace tr_(__func__, this);
+  const at::Device dev = device();
+  if (!dev.is_cuda()) fail("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  const devfn::Args bound = devfn::args_of(dev_args_);
+  enter(__func__, true, false, true);
+  if (kv) {
+    if (kv->n && !kv->device().is_cuda()) {
+      OocStats os;
+      ooc_for_each_kv_piece(*kv, ooc_env(), dev,
+                            [&](const KV& piece, int64_t first) { devfn::scan_pairs(piece, first, code, dev, bound); }, &os);
+      note_ooc("Scan", os);
+    } else if (kv->n) {
+      devfn::scan_pairs(*kv, 0, code, dev, bound);
+    }
+    stats("Scan", 0);
+    return count(kv->n);
+  }
+  need_kmv("scan");
+  OocStats os;
+  bool pieces = false;
+  for (const KMV& m : kmv_parts()) {
+    if (!m.nkey) continue;
+    if (!m.seg.is_cuda() || needs_ooc(m.nbytes(), budget(), 2.0)) {
+      pieces = true;
+      ooc_for_each_kmv_piece(m, ooc_env(), dev, [&](const KMV& piece) { devfn::scan_groups(piece, code, dev, bound); },
+                             &os);
+    } else {
+      devfn::scan_groups(m, code, dev, bound);
+    }
+  }
+  if (pieces) note_ooc("Scan", os);
+  stats("Scan", 1);
+  return count(kmv_keys());
 }
 
 uint64_t MapReduce::compress_builtin(const std::string& op, const std::string& dtype) {

@@ -144,6 +144,22 @@ class MapReduce {
   uint64_t sort_values_device(const std::string& code, int bits = 64);
   // every key's values of the KMV sorted by either functor; returns the global key count
   uint64_t sort_multivalues_device(const std::string& code, int bits = 64);
+  // The functors' user argument (MR-MPI's `ptr`): up to 8 device buffers that
+  // every later *_device call of this object hands to its functors (mrd::Args;
+  // mrd::MutArgs for scan_device). Each must be defined, contiguous and on
+  // this object's device (the error names the offending index). The object
+  // holds the tensors until they are replaced (an empty vector clears the
+  // binding), so a buffer cannot be freed under a running kernel; copy() does
+  // not carry the binding. The kernels run on the current stream: the buffers
+  // must be ready on it. New contents or new buffers never recompile a functor.
+  void set_device_args(std::vector<at::Tensor> bufs);
+  const std::vector<at::Tensor>& device_args() const { return dev_args_; }
+  // a read-only functor pass over the KV or the KMV, whichever the object
+  // holds: mr_scan (devfn.h) runs exactly once per pair / key and writes to
+  // the bound buffers; the data stays as it is. Returns the global pair / key
+  // count like scan_kv / scan_kmv. Data past the HBM budget is visited piece
+  // by piece; index is the pair's index on this rank.
+  uint64_t scan_device(const std::string& code);
   uint64_t convert();
   // convert with the keys' hash64_keys() already computed by the producer
   uint64_t convert_prehashed(const at::Tensor& prehash);
@@ -295,6 +311,7 @@ class MapReduce {
   // enabled (keyvalue.h); convert() uses it while it still describes kv
   std::shared_ptr<GroupIndex> grouped_;
   std::unique_ptr<KeyValue> open_;
+  std::vector<at::Tensor> dev_args_;  // set_device_args
   int open_add_ = 0;
   double t0_ = 0;
   int64_t cs0_ = 0, cr0_ = 0;

@@ -819,6 +819,16 @@ KV ooc_exchange(const KV& kv, const at::Tensor& dest_host, const Comm& comm, con
   return sink.finish(kv);
 }
 
+void ooc_for_each_kv_piece(const KV& kv, const OocEnv& env, at::Device dev,
+                           const std::function<void(const KV&, int64_t)>& fn, OocStats* st) {
+  const HostOff h = host_off(kv);
+  const int64_t cap = env.hbm > 0 ? std::max<int64_t>(env.hbm / 4, 1) : INT64_MAX;  // no budget: one piece
+  for (auto [a, b] : chunks(kv, h, cap)) {
+    fn(kv_to(kv_slice(kv, a, b, h.kp(), h.vp()), dev), a);
+    if (st) st->chunks++;
+  }
+}
+
 void ooc_for_each_kmv_block(const KMV& kmv, const OocEnv& env, at::Device dev,
                             const std::function<void(const KMV&, int)>& fn, bool split, OocStats* st) {
   const int64_t budget = env.hbm;

@@ -61,6 +61,11 @@ Upload upload_spool(Spool& sp, at::Device dev, const c10::optional<c10::hip::HIP
 KV ooc_sort(const KV& kv, int flag, bool by_value, const OocEnv& env, at::Device dev, OocStats* st = nullptr);
 KV ooc_reduce_builtin(const KMV& kmv, const std::string& op, const std::string& dtype, const OocEnv& env,
                       at::Device dev, OocStats* st = nullptr);
+// every pair range of a (host-resident) KV that fits a quarter of the budget,
+// as a device KV, to fn in order; first = the range's first pair in kv (the
+// read-only scan_device)
+void ooc_for_each_kv_piece(const KV& kv, const OocEnv& env, at::Device dev,
+                           const std::function<void(const KV&, int64_t first)>& fn, OocStats* st = nullptr);
 // every key range of a (host-resident) KMV whose values fit a quarter of the
 // budget, as a device KMV, to fn in key order (the reduce-family ops)
 void ooc_for_each_kmv_piece(const KMV& kmv, const OocEnv& env, at::Device dev, const std::function<void(const KMV&)>& fn,

@@ -176,6 +176,31 @@ void run_mr_method(Oink& o, int index, const Args& args) {
       else if (cmd == "sort_values/device") mr.sort_values_device(source(a[0]), bits);
       else mr.sort_multivalues_device(source(a[0]), bits);
     }
+  } else if (cmd == "scan/device") {
+    // scan/device file: mr_scan once per pair / key, results into the bound buffers
+    need(1, 1);
+    std::ifstream f(a[0]);
+    if (!f) throw Error("Cannot open device functor file " + a[0]);
+    std::stringstream ss;
+    ss << f.rdbuf();
+    mr.scan_device(ss.str());
+  } else if (cmd == "device_args") {
+    // device_args v1 v2 ...: the values as one float64 device buffer, argument
+    // 0 of every later */device command (a loop changes a parameter without
+    // recompiling the functor); no values clear the binding
+    std::vector<double> v;
+    for (const std::string& x : a) {
+      char* e = nullptr;
+      v.push_back(std::strtod(x.c_str(), &e));
+      if (!e || *e || x.empty()) throw Error("Illegal MR object device_args value " + x);
+    }
+    if (v.empty()) {
+      mr.set_device_args({});
+    } else {
+      at::Tensor t = at::empty({(int64_t)v.size()}, at::TensorOptions().dtype(at::kDouble));
+      std::memcpy(t.data_ptr(), v.data(), v.size() * sizeof(double));
+      mr.set_device_args({t.to(mr.device())});
+    }
   } else if (cmd == "print") {
     if (n == 4) mr.print(ival(a[0]), ival(a[1]), ival(a[2]), ival(a[3]));
     else if (n == 6) mr.print(a[0].c_str(), ival(a[1]), ival(a[2]), ival(a[3]), ival(a[4]), ival(a[5]));

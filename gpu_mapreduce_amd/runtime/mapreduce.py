@@ -293,21 +293,52 @@ class MapReduce(metaclass=_Counters):
         return self._m.compress_batch(lambda kmv, h: f(kmv, KeyValue.wrap(h)))
 
     # ---- device functors (csrc/engine/devfn.h): HIP device code compiled at run time
-    def map_device(self, src, code, addflag=0):
+    def device_args(self, *tensors):
+        """Bind up to 8 device buffers (contiguous tensors on this MR's
+        device): the functors' user argument, MR-MPI's `ptr`. Every later
+        *_device call hands them to its functors as `const mrd::Args& args`
+        (an optional trailing parameter of every entry point; scan_device's
+        mr_scan gets the writable `mrd::MutArgs`). The MR holds the tensors
+        until they are replaced; no tensors clears the binding. New contents
+        or new tensors never recompile a functor. The kernels run on the
+        current stream: the buffers must be ready on it."""
+        self._m.set_device_args(list(tensors))
+
+    @property
+    def bound_device_args(self):
+        """the tensors bound by device_args (a list, empty when none are)"""
+        return list(self._m.device_args())
+
+    def _with_args(self, args, call):
+        """`call()` under the binding `args` (None: the current one), the
+        previous binding back in place afterwards, also when the call raises"""
+        if args is None:
+            return call()
+        prev = self._m.device_args()
+        self._m.set_device_args(list(args))
+        try:
+            return call()
+        finally:
+            self._m.set_device_args(prev)
+
+    def map_device(self, src, code, addflag=0, args=None):
         """map with a device functor: `src` a MapReduce (every pair through
         `__device__ void mr_map(mrd::Bytes key, mrd::Bytes value, long long
-        index, mrd::Emit& out)`) or a task count (key / value empty, index =
-        the task). One GPU thread per pair / task; no host round trip."""
+        index, mrd::Emit& out[, const mrd::Args& args])`) or a task count
+        (key / value empty, index = the task). One GPU thread per pair /
+        task; no host round trip. `args=` (here and on the other *_device
+        calls) binds device buffers for this call only, see device_args."""
         if isinstance(src, int):
-            return self._m.map_device_tasks(int(src), code, addflag)
-        return self._m.map_device(src._m, code, addflag)
+            return self._with_args(args, lambda: self._m.map_device_tasks(int(src), code, addflag))
+        return self._with_args(args, lambda: self._m.map_device(src._m, code, addflag))
 
-    def reduce_device(self, code):
+    def reduce_device(self, code, args=None):
         """reduce with a device functor: every key through `__device__ void
-        mr_reduce(mrd::Bytes key, mrd::Values values, mrd::Emit& out)`."""
-        return self._m.reduce_device(code)
+        mr_reduce(mrd::Bytes key, mrd::Values values, mrd::Emit& out[, const
+        mrd::Args& args])`."""
+        return self._with_args(args, lambda: self._m.reduce_device(code))
 
-    def sort_keys_device(self, code, bits=64):
+    def sort_keys_device(self, code, bits=64, args=None):
         """stable sort by a device sort functor, in one of two forms.
         `__device__ unsigned long long mr_sortkey(mrd::Bytes key)` maps each
         key to a 64-bit key whose unsigned order is the wanted one (a
@@ -316,22 +347,32 @@ class MapReduce(metaclass=_Counters):
         `__device__ int mr_compare(mrd::Bytes a, mrd::Bytes b)` (< 0 a first,
         0 equal, > 0 b first; a strict weak order) is for every other order:
         a merge sort on the GPU, `bits` ignored. Code naming both takes the
-        mr_sortkey form."""
-        return self._m.sort_keys_device(code, bits)
+        mr_sortkey form. Either may take a trailing `const mrd::Args& args`."""
+        return self._with_args(args, lambda: self._m.sort_keys_device(code, bits))
 
-    def sort_values_device(self, code, bits=64):
+    def sort_values_device(self, code, bits=64, args=None):
         """sort_keys_device over the values (either functor form)."""
-        return self._m.sort_values_device(code, bits)
+        return self._with_args(args, lambda: self._m.sort_values_device(code, bits))
 
-    def sort_multivalues_device(self, code, bits=64):
+    def sort_multivalues_device(self, code, bits=64, args=None):
         """every key's values of the KMV sorted by a device sort functor
         (mr_sortkey or mr_compare, as sort_keys_device); returns the global
         key count."""
-        return self._m.sort_multivalues_device(code, bits)
+        return self._with_args(args, lambda: self._m.sort_multivalues_device(code, bits))
 
-    def compress_device(self, code):
+    def compress_device(self, code, args=None):
         """compress (local groups, no shuffle) with a device reduce functor."""
-        return self._m.compress_device(code)
+        return self._with_args(args, lambda: self._m.compress_device(code))
+
+    def scan_device(self, code, args=None):
+        """read-only pass with a device functor over the KV or the KMV,
+        whichever this MR holds: `__device__ void mr_scan(mrd::Bytes key,
+        mrd::Bytes value, long long index, const mrd::MutArgs& args)` or
+        `mr_scan(mrd::Bytes key, mrd::Values values, const mrd::MutArgs&
+        args)` runs exactly once per pair / key and writes its results into
+        the bound buffers (atomics, or plain stores to distinct slots). The
+        data is left as it is; returns the global pair / key count."""
+        return self._with_args(args, lambda: self._m.scan_device(code))
 
     def scan_kv(self, fn, ptr=None):
         """Read-only fn(key, value[, ptr]) over the KV (reference :1933-1976)."""
