@@ -4,24 +4,26 @@
 // kernels and run over device-resident KV / KMV columns. No ATen tensor
 // program and no host round trip: one thread per pair (map) or per key
 // (reduce), the emitted records sized by a count pass, placed by exclusive
-// scans and written by a second pass (devfn.cpp).
+// scans and written by a second pass (devfn.cpp; the device text is
+// devfn_text.cpp).
 //
 // User code defines one of
 //   __device__ void mr_map(mrd::Bytes key, mrd::Bytes value, long long index, mrd::Emit& out);
 //   __device__ void mr_reduce(mrd::Bytes key, mrd::Values values, mrd::Emit& out);
 // and emits with out.emit(kptr, kbytes, vptr, vbytes) or out.emit(k, v) for
 // trivially copyable k, v. It must be a pure function of its arguments (it
-// runs twice: count, then write). The prelude (kDevicePrelude in devfn.cpp)
-// documents mrd::Bytes / mrd::Values / mrd::Emit.
+// runs twice: count, then write). The prelude (text::kPrelude in
+// devfn_text.cpp) documents mrd::Bytes / mrd::Values / mrd::Emit.
 //
 // The user argument (MR-MPI's `ptr`): up to kMaxArgs device buffers bound to
 // the MapReduce object (set_device_args) reach every functor kernel as ONE
 // by-value kernel argument, a struct of 8 x {pointer, byte count} and a count
-// (Args below = mrd::Args in the prelude). No global symbol in the module, no
-// allocation, nothing shared between two ops that run one cached module; the
-// module cache key stays (device, kind, code), so new contents or new buffers
-// never recompile. Every entry point (mr_map, mr_reduce, mr_init, mr_add,
-// mr_merge, mr_finish, mr_sortkey, mr_compare) MAY take one trailing
+// (Args below = mrd::Args in the prelude; both sides assert the layout). No
+// global symbol in the module, no allocation, nothing shared between two ops
+// that run one cached module; the module cache key stays (device, kind, scan
+// shape, code), so new contents or new buffers never recompile. Every entry
+// point (mr_map, mr_reduce, mr_init, mr_add, mr_merge, mr_finish, mr_sortkey,
+// mr_compare) MAY take one trailing
 // `const mrd::Args& args` parameter, each function on its own; args[i] is
 // {p, n bytes} ({nullptr, 0} past the bound count), args[i].as<T>() a
 // `const T*`, args[i].count<T>() the number of T. These functors run more than
@@ -29,7 +31,7 @@
 // buffers are read-only to them, and the purity rule now reads "a pure
 // function of its arguments and the bound buffers' contents".
 //
-// scan (kind 5) is the one functor that writes to the bound buffers:
+// scan (Kind::Scan) is the one functor that writes to the bound buffers:
 //   __device__ void mr_scan(mrd::Bytes key, mrd::Bytes value, long long index, const mrd::MutArgs& args);  // KV
 //   __device__ void mr_scan(mrd::Bytes key, mrd::Values values, const mrd::MutArgs& args);                 // KMV
 // runs exactly once per item (one thread each) and emits nothing; it writes
@@ -48,6 +50,9 @@
 
 namespace mrh {
 namespace devfn {
+// the functor kinds: mr_map; mr_reduce per key; the fold form (mr_init / mr_add
+// / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan
+enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan };
 // the bound buffers as every functor kernel takes them (layout of mrd::Args /
 // mrd::MutArgs in the prelude); slots past n are {nullptr, 0}
 constexpr int kMaxArgs = 8;
@@ -92,9 +97,9 @@ at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, in
 int64_t compile_check_compare(const std::string& code);
 // rows per workgroup tile of the comparator sort (a power of two)
 int64_t compare_tile();
-// which sort functor the code defines: 3 = mr_sortkey (wins when both names
-// appear), 4 = mr_compare; neither is an error that names both
-int sort_kind_of(const std::string& code);
+// which sort functor the code defines: SortKey = mr_sortkey (wins when both
+// names appear), Compare = mr_compare; neither is an error that names both
+Kind sort_kind_of(const std::string& code);
 // scan functor (mr_scan, see above) over the pairs of kv (on the GPU; index =
 // base + the pair's position in kv) / over every key of m; returns the items visited
 int64_t scan_pairs(const KV& kv, int64_t base, const std::string& code, at::Device dev, const Args& args);

@@ -1378,6 +1378,14 @@ int64_t functor_chunk(const KeyValue& out, int64_t n) {
   const int64_t pb = out.piece_bytes();
   return pb > 0 ? std::max<int64_t>(4096, pb / 128) : std::max<int64_t>(n, 1);
 }
+// reduce_device / compress_device: the groups a batch op hands over, through the functor
+ReduceBatchFn functor_reduce(const std::string& code, at::Device dev, const devfn::Args& bound) {
+  return [=](const KMV& m, KeyValue& out) {
+    if (!m.nkey) return;
+    KV o = devfn::reduce_groups(m, code, dev, bound);
+    if (o.n) out.add_kv(o);
+  };
+}
 }  // namespace
 
 void MapReduce::set_device_args(std::vector<at::Tensor> bufs) {
@@ -1434,13 +1442,7 @@ uint64_t MapReduce::map_device_tasks(int64_t ntask, const std::string& code, int
 }
 
 uint64_t MapReduce::reduce_device(const std::string& code) {
-  const at::Device dev = device();
-  const devfn::Args bound = devfn::args_of(dev_args_);
-  return reduce_batch([&](const KMV& m, KeyValue& out) {
-    if (!m.nkey) return;
-    KV o = devfn::reduce_groups(m, code, dev, bound);
-    if (o.n) out.add_kv(o);
-  });
+  return reduce_batch(functor_reduce(code, device(), devfn::args_of(dev_args_)));
 }
 
 namespace {
@@ -1448,13 +1450,14 @@ namespace {
 // mr_sortkey -> radix sort of its 64-bit keys; mr_compare -> the merge sort
 KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_value, at::Device dev,
                    const devfn::Args& bound) {
-  const int kind = devfn::sort_kind_of(code);
+  const devfn::Kind kind = devfn::sort_kind_of(code);
   if (kv_in.n <= 1) return kv_in;
   const KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
   const at::Tensor& data = by_value ? kv.vdata : kv.kdata;
   const at::Tensor& off = by_value ? kv.voff : kv.koff;
   const int w = by_value ? kv.vw : kv.kw;
-  if (kind == 4) return gather(kv, devfn::compare_perm(data, off, w, kv.n, at::Tensor(), code, dev, bound));
+  if (kind == devfn::Kind::Compare)
+    return gather(kv, devfn::compare_perm(data, off, w, kv.n, at::Tensor(), code, dev, bound));
   auto [key, idx] = devfn::sort_keys_of(data, off, w, kv.n, code, dev, bound);
   auto [ks, perm, passes] = radix_sort_pairs(key, idx, 0, std::max(1, std::min(bits, 64)));
   (void)ks;
@@ -1463,24 +1466,24 @@ KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_v
 }
 }  // namespace
 
-uint64_t MapReduce::sort_keys_device(const std::string& code, int bits) {
+// sort_keys_device / sort_values_device: op = the caller's name, what / heading as need_kv / stats print them
+uint64_t MapReduce::sort_column_device(const char* op, const char* what, const char* heading, bool by_value,
+                                       const std::string& code, int bits) {
   start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
-  need_kv("sort_keys");
-  kv = sort_by_functor(*kv, code, bits, false, device(), devfn::args_of(dev_args_));
-  stats("Sort_keys", 0);
+  OpTrace tr_(op, this);
+  enter(op);
+  need_kv(what);
+  kv = sort_by_functor(*kv, code, bits, by_value, device(), devfn::args_of(dev_args_));
+  stats(heading, 0);
   return count(kv->n);
 }
 
+uint64_t MapReduce::sort_keys_device(const std::string& code, int bits) {
+  return sort_column_device(__func__, "sort_keys", "Sort_keys", false, code, bits);
+}
+
 uint64_t MapReduce::sort_values_device(const std::string& code, int bits) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
-  need_kv("sort_values");
-  kv = sort_by_functor(*kv, code, bits, true, device(), devfn::args_of(dev_args_));
-  stats("Sort_values", 0);
-  return count(kv->n);
+  return sort_column_device(__func__, "sort_values", "Sort_values", true, code, bits);
 }
 
 uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
@@ -1488,19 +1491,13 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
   OpTrace tr_("sort_multivalues", this);
   enter("sort_multivalues");
   need_kmv("sort_multivalues");
-  const int kind = devfn::sort_kind_of(code);
+  const devfn::Kind kind = devfn::sort_kind_of(code);
   const at::Device dev = device();
   const devfn::Args bound = devfn::args_of(dev_args_);
   if (kmv->nval > 1) {
-    KMV m = *kmv;
-    if (m.seg.device() != dev) {
-      m.keys = kv_to(m.keys, dev);
-      m.vdata = m.vdata.to(dev);
-      if (m.voff.defined()) m.voff = m.voff.to(dev);
-      m.seg = m.seg.to(dev);
-    }
+    KMV m = kmv->seg.device() == dev ? *kmv : kmv_to(*kmv, dev, false);
     at::Tensor perm;
-    if (kind == 4) {
+    if (kind == devfn::Kind::Compare) {
       // the values are grouped by key already: one sort under (segment id, mr_compare)
       perm = devfn::compare_perm(m.vdata, m.voff, m.vw, m.nval, segment_ids(m.seg, m.nkey, m.nval), code, dev,
                                  bound);
@@ -1526,13 +1523,7 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
 }
 
 uint64_t MapReduce::compress_device(const std::string& code) {
-  const at::Device dev = device();
-  const devfn::Args bound = devfn::args_of(dev_args_);
-  return compress_batch([&](const KMV& m, KeyValue& out) {
-    if (!m.nkey) return;
-    KV o = devfn::reduce_groups(m, code, dev, bound);
-    if (o.n) out.add_kv(o);
-  });
+  return compress_batch(functor_reduce(code, device(), devfn::args_of(dev_args_)));
 }
 
 // scan with a device functor: the data stays where and as it is. Pairs /

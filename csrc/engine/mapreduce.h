@@ -276,6 +276,8 @@ class MapReduce {
   void stats(const char* heading, int which);
   void need_kv(const char* what) const;
   void need_kmv(const char* what) const;
+  uint64_t sort_column_device(const char* op, const char* what, const char* heading, bool by_value,
+                              const std::string& code, int bits);
   void note_shuffle(const ShuffleStats& st);
   uint64_t count(int64_t n) const { return (uint64_t)comm_->allreduce(n, Comm::SUM); }
   std::vector<int> my_tasks(int nmap);
