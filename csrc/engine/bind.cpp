@@ -986,6 +986,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("device_compare_tile", &devfn::compare_tile);
   m.def("device_scan_check", &devfn::compile_check_scan, py::arg("code"), py::arg("kmv"),
         py::call_guard<py::gil_scoped_release>());
+  m.def("device_hash_check", &devfn::compile_check_hash, py::arg("code"), py::call_guard<py::gil_scoped_release>());
+  // the owners mr_hash gives the pairs of a device KV among nprocs ranks (int32 [n]); one process
+  m.def(
+      "device_hash_dest",
+      [](const KV& kv, int nprocs, const std::string& code, const std::vector<at::Tensor>& args) {
+        for (const at::Tensor& t : args)
+          if (!t.defined() || !t.is_contiguous() || t.device() != kv.device())
+            throw std::runtime_error("mrhip: device_hash_dest: the bound buffers are contiguous tensors on the KV's device");
+        return devfn::hash_dest(kv, nprocs, code, kv.device(), devfn::args_of(args));
+      },
+      py::arg("kv"), py::arg("nprocs"), py::arg("code"), py::arg("args") = std::vector<at::Tensor>(),
+      py::call_guard<py::gil_scoped_release>());
   m.def("device_functor_compiles", &devfn::compile_count);
   m.def("host_arena_reserve", &hostarena::reserve, py::call_guard<py::gil_scoped_release>());
   m.def("host_arena_stats", [] {

@@ -51,6 +51,7 @@ enum EmitFn { kCount, kWrite, kAccSize, kFoldNChunks, kFoldChunks, kFoldMerge };
 enum SortKeyFn { kSortKey };
 enum CompareFn { kBlockSort, kMerge };
 enum ScanFn { kScan };
+enum HashFn { kHash };
 constexpr int kMaxEntries = 6;
 
 struct KindRow {
@@ -74,6 +75,7 @@ struct KindRow {
 //   mrd_cmp_blocksort (col, const i64* sid, i64 n, u32* out, Args)
 //   mrd_cmp_merge     (col, const i64* sid, i64 n, const u32* src, u32* dst, i64 W, Args)
 //   mrd_scan          (items, i64 base, i64 n, MutArgs)
+//   mrd_hash          (col, i64 n, int P, int* dest, Args)
 const KindRow kKinds[] = {
     {"mrd_map.hip", "MRD_REDUCE", 0, text::kEmitKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
     {"mrd_reduce.hip", "MRD_REDUCE", 1, text::kEmitKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
@@ -84,6 +86,7 @@ const KindRow kKinds[] = {
     {"mrd_compare.hip", "MRD_CMP_T", kCompareTile, text::kCompareKernels, {"mrd_cmp_blocksort", "mrd_cmp_merge"},
      "the comparator functor's"},
     {"mrd_scan.hip", "MRD_SCAN_KMV", 0, text::kScanKernel, {"mrd_scan"}, "the scan functor's"},
+    {"mrd_hash.hip", nullptr, 0, text::kHashKernel, {"mrd_hash"}, "the partitioner functor's"},
 };
 const KindRow& row_of(Kind kind) { return kKinds[(int)kind]; }
 
@@ -153,6 +156,17 @@ const Module& module_for(const std::string& code, Kind kind, int device, bool km
     throw std::runtime_error(std::string("mrhip: loading ") + r.whose + " code object failed");
   }
   return *cache.emplace(key, std::move(m)).first->second;
+}
+
+// a partitioner source without its entry point would only fail inside the call
+// shim. A heuristic (a substring search, as sort_kind_of): code that names
+// mr_hash only in a comment or as part of a longer name passes it and gets the
+// shim's compiler log instead
+void need_hash(const std::string& code) {
+  if (code.find("mr_hash") == std::string::npos)
+    throw std::runtime_error(
+        "mrhip: a device partitioner functor defines `int mr_hash(mrd::Bytes key)` (MR-MPI's hash callback: the "
+        "pair's owner is the result mod the number of ranks); the code has no mr_hash");
 }
 
 void need_gpu(at::Device dev) {
@@ -310,6 +324,10 @@ int64_t compile_check(const std::string& code, bool reduce) { return check(code,
 int64_t compile_check_sortkey(const std::string& code) { return check(code, Kind::SortKey); }
 int64_t compile_check_compare(const std::string& code) { return check(code, Kind::Compare); }
 int64_t compile_check_scan(const std::string& code, bool kmv) { return check(code, Kind::Scan, kmv); }
+int64_t compile_check_hash(const std::string& code) {
+  need_hash(code);
+  return check(code, Kind::Hash);
+}
 int64_t compile_count() { return g_compiles.load(); }
 int64_t compare_tile() { return kCompareTile; }
 
@@ -392,6 +410,21 @@ at::Tensor compare_perm(const at::Tensor& data, const at::Tensor& off, int w, in
     std::swap(a, b);
   }
   return a;
+}
+
+at::Tensor hash_dest(const KV& kv, int P, const std::string& code, at::Device dev, const Args& bound) {
+  need_gpu(dev);
+  need_hash(code);
+  if (P < 1) throw std::runtime_error("mrhip: hash_dest: " + std::to_string(P) + " ranks");
+  if (kv.n > 0 && kv.device() != dev) throw std::runtime_error("mrhip: hash_dest needs the keys in HBM");
+  // (the module first: no pairs still means a functor that compiles)
+  const Module& m = module_for(code, Kind::Hash, dev.index());
+  at::Tensor dest = at::empty({std::max<int64_t>(kv.n, 0)}, opt(dev, at::kInt));
+  if (kv.n <= 0) return dest;
+  const Column c = column_of(kv.kdata, kv.koff, kv.kw);
+  launch(m.fn[kHash], grid_of(kv.n), at::hip::getCurrentHIPStream(), c.d, c.off, c.w, kv.n, P, P0<int32_t>(dest),
+         bound);
+  return dest;
 }
 
 int64_t scan_pairs(const KV& kv_in, int64_t base, const std::string& code, at::Device dev, const Args& bound) {

@@ -23,7 +23,7 @@
 // that run one cached module; the module cache key stays (device, kind, scan
 // shape, code), so new contents or new buffers never recompile. Every entry
 // point (mr_map, mr_reduce, mr_init, mr_add, mr_merge, mr_finish, mr_sortkey,
-// mr_compare) MAY take one trailing
+// mr_compare, mr_hash) MAY take one trailing
 // `const mrd::Args& args` parameter, each function on its own; args[i] is
 // {p, n bytes} ({nullptr, 0} past the bound count), args[i].as<T>() a
 // `const T*`, args[i].count<T>() the number of T. These functors run more than
@@ -51,8 +51,8 @@
 namespace mrh {
 namespace devfn {
 // the functor kinds: mr_map; mr_reduce per key; the fold form (mr_init / mr_add
-// / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan
-enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan };
+// / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan; mr_hash
+enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan, Hash };
 // the bound buffers as every functor kernel takes them (layout of mrd::Args /
 // mrd::MutArgs in the prelude); slots past n are {nullptr, 0}
 constexpr int kMaxArgs = 8;
@@ -106,6 +106,16 @@ int64_t scan_pairs(const KV& kv, int64_t base, const std::string& code, at::Devi
 int64_t scan_groups(const KMV& m, const std::string& code, at::Device dev, const Args& args);
 // compile only (kmv: the KMV shape of mr_scan); the code object size in bytes
 int64_t compile_check_scan(const std::string& code, bool kmv);
+// partitioner functor: `__device__ int mr_hash(mrd::Bytes key)`, MR-MPI's
+// hash callback (int hash(char* key, int keybytes)), once per pair and a pure
+// function of the key and the bound buffers' contents. Returns the owner of
+// every pair of kv (on the GPU), int32 [kv.n]: ((long long)h % P + P) % P, so
+// negative returns and INT_MIN land where the host route puts them. P is a
+// kernel argument: a new world size never recompiles. n == 0: no launch.
+at::Tensor hash_dest(const KV& kv, int P, const std::string& code, at::Device dev, const Args& args = Args{});
+// compile only; the code object size in bytes. Works without a GPU. A source
+// without mr_hash is an error that names it (here and in hash_dest).
+int64_t compile_check_hash(const std::string& code);
 // hiprtc compilations this process has done so far (checks and module loads alike)
 int64_t compile_count();
 // the full source handed to the compiler (prelude + code + kernels)

@@ -519,6 +519,23 @@ mrd_scan(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd
 }
 )MRD";
 
+// a partitioner functor, __device__ int mr_hash(mrd::Bytes key) (MR-MPI's
+// hash callback): the owner of pair i is its return value reduced into
+// [0, P) the way the host route does it, negative returns included
+const char kHashKernel[] = R"MRD(
+// ---- mrd partitioner kernel ----
+namespace mrd {
+MRD_SHIM(hash, (class B), (B b), (b))
+}  // namespace mrd
+extern "C" __global__ __launch_bounds__(256) void
+mrd_hash(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, int P, int* dest, mrd::Args args) {
+  for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
+    const int h = mrd::call_hash(mrd::row(d, off, w, i), args, 0);
+    dest[i] = (int)(((mrd::i64)h % P + P) % P);
+  }
+}
+)MRD";
+
 }  // namespace text
 }  // namespace devfn
 }  // namespace mrh
