@@ -50,7 +50,7 @@ PG as_pg(py::object o) {
 // Run a collective native op (graph plans, their iterations); if it throws on
 // a multi-rank communicator, poison the job before the error reaches Python,
 // so peers blocked in the same collective fail within seconds instead of
-// waiting on a rank that has moved on (MapReduce ops do this in OpTrace).
+// waiting on a rank that has moved on (MapReduce ops do this in their op frame).
 template <typename F>
 auto poisoning(const CommPtr& c, const char* what, F&& f) -> decltype(f()) {
   try {

@@ -45,83 +45,10 @@ std::function<void(const std::string&)>& screen_sink() {
 
 namespace {
 
-// roctx range per MapReduce op: `rocprofv3 --marker-trace` shows every op
-// (map, aggregate, convert, reduce, ...) around its kernels and RCCL calls
-// On scope exit (after the op's return value is computed) an MR with
-// outofcore == 1 writes its data to disk — the reference's forced
-// out-of-core mode (src/keyvalue.cpp:122,223); the next op reads it back.
-//
-// With MRH_TRACE set, every op also appends a JSON line (guard.h trace_op):
-// wall time with the device synchronised at both ends, local pair counts and
-// bytes, and the bytes this rank sent/received in shuffles during the op.
 thread_local int g_op_depth = 0;
 void device_sync(const MapReduce* mr) {
   if (mr->device().is_cuda()) guard::hip_check(hipDeviceSynchronize(), "trace_sync", mr->comm()->rank());
 }
-struct OpTrace {
-  OpTrace(const char* name, MapReduce* mr) : mr_(mr), name_(name) {
-    roctxRangePushA(name);
-    if (g_op_depth == 0) guard::set_current_op(name);
-    // page pool installed + a page budget B: the op may hold at most 2B of
-    // new device memory (output + working set) plus 16 MiB of kernel scratch
-    // (sort histograms, scan partials, size-class rounding); past it an
-    // allocation fails with "Cannot allocate page" (reference mem_request at
-    // maxpage)
-    if (g_op_depth == 0 && hbm::installed() && mr->device().is_cuda() && mr->budget() > 0)
-      cap_.emplace(mr->device().index() < 0 ? 0 : mr->device().index(), 2 * mr->budget() + (int64_t(16) << 20));
-    if (guard::trace_enabled()) {
-      device_sync(mr);
-      t0_ = Comm::wtime();
-      s0_ = MapReduce::cssize.load();
-      r0_ = MapReduce::crsize.load();
-    }
-    ++g_op_depth;
-  }
-  ~OpTrace() {
-    --g_op_depth;
-    if (std::uncaught_exceptions() > 0 && g_op_depth == 0 && mr_->comm()->size() > 1) {
-      // an op failing on one rank can never complete its collectives on the
-      // others: fail the whole job now (reference Error::one -> MPI_Abort,
-      // src/error.cpp:47-57) instead of leaving peers blocked in a shuffle
-      mr_->comm()->poison(std::string("MapReduce ") + name_ + " raised an error on rank " +
-                          std::to_string(mr_->my_proc()));
-    }
-    if (guard::trace_enabled() && std::uncaught_exceptions() == 0) {
-      device_sync(mr_);
-      const double t1 = Comm::wtime();
-      int64_t b = 0;
-      if (mr_->kv) b += mr_->kv->nbytes();
-      for (const KMV& m : mr_->kmv_parts()) b += m.nbytes();
-      guard::trace_op(mr_->my_proc(), name_, mr_->instance(), g_op_depth, t0_, (t1 - t0_) * 1e3,
-                      mr_->kv ? mr_->kv->n : 0, mr_->kmv_keys(), b, MapReduce::cssize.load() - s0_,
-                      MapReduce::crsize.load() - r0_);
-    }
-    // freepage (reference: pages freed after every op, src/mapreduce.cpp:
-    // 3483-3517): with an HBM budget in force, blocks the op freed go back to
-    // the driver too, so the footprint between ops stays within the budget
-    if (mr_->set.freepage && mr_->budget() > 0 && g_op_depth == 0 && mr_->device().is_cuda() &&
-        std::uncaught_exceptions() == 0)
-      c10::hip::HIPCachingAllocator::emptyCache();
-    // MRH_GUARD: every live block's canaries at the end of each top-level op
-    if (g_op_depth == 0 && guard::alloc_guard_active()) {
-      guard::check_all_blocks(name_);
-      guard::set_current_op(nullptr);
-    }
-    if (mr_->set.outofcore == 1 && std::uncaught_exceptions() == 0) {
-      try {
-        mr_->spill_disk();
-      } catch (const std::exception& e) {
-        std::fprintf(stderr, "mrhip: out-of-core write failed: %s\n", e.what());
-      }
-    }
-    roctxRangePop();
-  }
-  MapReduce* mr_;
-  const char* name_;
-  double t0_ = 0;
-  int64_t s0_ = 0, r0_ = 0;
-  std::optional<hbm::OpCap> cap_;
-};
 
 [[noreturn]] void fail(const std::string& m) { throw std::runtime_error(m); }
 
@@ -309,6 +236,207 @@ struct ChunkTask {
 
 }  // namespace
 
+// ====================================================================== op frame
+
+// The frame every op runs in: a stack object constructed at the top of the
+// op, the only thing an op needs for protocol. It holds the op's start state
+// (wall clock and comm counters, read once: the stats lines and the MRH_TRACE
+// record both measure from them), so an op that runs other ops (collate,
+// scrunch) keeps its own.
+//
+// Construction opens a roctx range (`rocprofv3 --marker-trace` shows every op
+// around its kernels and RCCL calls) and, with MRH_TRACE set, the op's trace
+// record (guard.h trace_op: wall time with the device synchronised at both
+// ends, local pair counts and bytes, the bytes this rank sent / received in
+// shuffles), then runs the entry protocol (enter). The finishers print the
+// stats and return the global count. On scope exit, after the return value
+// is computed, an MR with outofcore == 1 writes its data to disk — the
+// reference's forced out-of-core mode (src/keyvalue.cpp:122,223); the next op
+// reads it back.
+class MapReduce::Op {
+ public:
+  struct Deferred {};
+  // the map family drops the data it replaces (drop_for_map) after the trace
+  // opens and before the entry protocol: it calls enter() itself
+  Op(MapReduce* mr, const char* name, Deferred) : mr_(mr), name_(name) {
+    if (mr->set.timer == 1) mr->comm_->barrier();
+    mark();
+    roctxRangePushA(name);
+    if (g_op_depth == 0) guard::set_current_op(name);
+    // page pool installed + a page budget B: the op may hold at most 2B of
+    // new device memory (output + working set) plus 16 MiB of kernel scratch
+    // (sort histograms, scan partials, size-class rounding); past it an
+    // allocation fails with "Cannot allocate page" (reference mem_request at
+    // maxpage)
+    if (g_op_depth == 0 && hbm::installed() && mr->device().is_cuda() && mr->budget() > 0)
+      cap_.emplace(mr->device().index() < 0 ? 0 : mr->device().index(), 2 * mr->budget() + (int64_t(16) << 20));
+    if (guard::trace_enabled()) device_sync(mr);
+    ++g_op_depth;
+  }
+  // parts_ok: the op reads the appended KV parts itself (else they are
+  // flattened); kmv_parts_ok: the same for the KMV's parts
+  Op(MapReduce* mr, const char* name, bool ooc_ok = false, bool parts_ok = false, bool kmv_parts_ok = false)
+      : Op(mr, name, Deferred()) {
+    enter(ooc_ok, parts_ok, kmv_parts_ok);
+  }
+  // close(): the end of an open() .. close() span, not an op of its own (no
+  // trace record, no entry protocol); its stats measure from here
+  explicit Op(MapReduce* mr) : mr_(mr), name_(nullptr) { mark(); }
+  Op(const Op&) = delete;
+  Op& operator=(const Op&) = delete;
+
+  ~Op() {
+    if (!name_) return;
+    --g_op_depth;
+    if (std::uncaught_exceptions() > 0 && g_op_depth == 0 && mr_->comm()->size() > 1) {
+      // an op failing on one rank can never complete its collectives on the
+      // others: fail the whole job now (reference Error::one -> MPI_Abort,
+      // src/error.cpp:47-57) instead of leaving peers blocked in a shuffle
+      mr_->comm()->poison(std::string("MapReduce ") + name_ + " raised an error on rank " +
+                          std::to_string(mr_->my_proc()));
+    }
+    if (guard::trace_enabled() && std::uncaught_exceptions() == 0) {
+      device_sync(mr_);
+      const double t1 = Comm::wtime();
+      int64_t b = 0;
+      if (mr_->kv) b += mr_->kv->nbytes();
+      for (const KMV& m : mr_->kmv_parts()) b += m.nbytes();
+      guard::trace_op(mr_->my_proc(), name_, mr_->instance(), g_op_depth, began_, (t1 - began_) * 1e3,
+                      mr_->kv ? mr_->kv->n : 0, mr_->kmv_keys(), b, cssize.load() - sent0_, crsize.load() - recv0_);
+    }
+    // freepage (reference: pages freed after every op, src/mapreduce.cpp:
+    // 3483-3517): with an HBM budget in force, blocks the op freed go back to
+    // the driver too, so the footprint between ops stays within the budget
+    if (mr_->set.freepage && mr_->budget() > 0 && g_op_depth == 0 && mr_->device().is_cuda() &&
+        std::uncaught_exceptions() == 0)
+      c10::hip::HIPCachingAllocator::emptyCache();
+    // MRH_GUARD: every live block's canaries at the end of each top-level op
+    if (g_op_depth == 0 && guard::alloc_guard_active()) {
+      guard::check_all_blocks(name_);
+      guard::set_current_op(nullptr);
+    }
+    if (mr_->set.outofcore == 1 && std::uncaught_exceptions() == 0) {
+      try {
+        mr_->spill_disk();
+      } catch (const std::exception& e) {
+        std::fprintf(stderr, "mrhip: out-of-core write failed: %s\n", e.what());
+      }
+    }
+    roctxRangePop();
+  }
+
+  // every op's entry: fault injection point, and data spilled to host (spill()
+  // or spill-on-OOM) comes back to HBM before the op touches it
+  void enter(bool ooc_ok = false, bool parts_ok = false, bool kmv_parts_ok = false) {
+    MapReduce& m = *mr_;
+    guard::fault_point(name_, m.comm_->rank());
+    if (!parts_ok) m.flatten();
+    if (!kmv_parts_ok) m.flatten_kmv();
+    if (guard::alloc_guard_active()) {  // an overrun found at the end of an earlier op fails the next one
+      static size_t raised = 0;
+      const auto reps = guard::guard_reports();
+      if (reps.size() > raised) {
+        const guard::GuardReport& r = reps[raised];
+        raised = reps.size();
+        throw std::runtime_error("mrhip guard: out-of-bounds device write into a " + std::to_string(r.size) +
+                                 "-byte block allocated in " + r.alloc_op + ", detected " + r.found_op);
+      }
+    }
+    if (!m.started_) {
+      m.started_ = true;
+      // minpage (reference allocate(), src/mapreduce.cpp:3318-3357): pages
+      // claimed up front; here the caching allocator's pool is grown by
+      // minpage x memsize once, so the first ops do not pay for hipMalloc
+      if (m.set.minpage > 0 && m.device().is_cuda()) {
+        at::Tensor t = at::empty({(int64_t)m.set.minpage * m.block_bytes()},
+                                 at::TensorOptions().device(m.device()).dtype(at::kByte));
+      }
+    }
+    m.ensure_resident();
+    // a group-by index outlives its KV only until the next op sees the KV changed
+    if (m.grouped_ && (!m.kv || !m.grouped_->describes(*m.kv))) m.grouped_.reset();
+    const bool on_host = (m.kv && !m.kv->device().is_cuda()) || (m.kmv && !m.kmv->keys.device().is_cuda());
+    if (!m.device().is_cuda() || !on_host) return;
+    // an op with an out-of-core path leaves host-resident data larger than the
+    // HBM budget where it is and streams it; every other op brings it back
+    if (ooc_ok && needs_ooc(m.data_bytes(), m.budget(), 2.0)) return;
+    m.unspill();
+  }
+
+  // The finishers: the op's stats lines, then the global count it returns.
+  // These are the pairs of the KV / the keys of the KMV with their appended
+  // parts. Where an op used to count kv->n or kmv->nkey alone it had entered
+  // with parts_ok / kmv_parts_ok false, so the parts were flattened at entry
+  // and its body assigns kv / kmv whole: the tail is empty and the two agree.
+  uint64_t kv_done(const char* heading) {
+    stats(heading, 0);
+    return mr_->count(mr_->kv_rows());
+  }
+  uint64_t kmv_done(const char* heading) {
+    stats(heading, 1);
+    return mr_->count(mr_->kmv_keys());
+  }
+
+ private:
+  void mark() {
+    began_ = Comm::wtime();
+    sent0_ = cssize.load();
+    recv0_ = crsize.load();
+  }
+
+  // per-op stats (reference :3112-3179)
+  void stats(const char* heading, int which) {
+    MapReduce& m = *mr_;
+    Comm& comm = *m.comm_;
+    if (guard::check_enabled()) {
+      if (m.kv) guard::check_kv(*m.kv, heading);
+      for (const KMV& p : m.kmv_parts()) guard::check_kmv(p, heading);
+    }
+    const int64_t b = m.data_bytes();
+    msize = b;
+    if (b > msizemax) msizemax = b;
+    if (m.set.timer == 1) {
+      comm.barrier();
+      if (comm.rank() == 0) out(fmt("%s time (secs) = %g\n", heading, Comm::wtime() - began_));
+    } else if (m.set.timer == 2) {
+      m.histo(Comm::wtime() - began_, (std::string(heading) + " time (secs) =").c_str());
+    }
+    if (m.set.verbosity == 0) return;
+    if (comm.rank() == 0) out(std::string(heading) + (which == 0 ? " KV = " : " KMV = "));
+    if (which == 0) m.kv_stats(m.set.verbosity);
+    else m.kmv_stats(m.set.verbosity);
+    std::vector<int64_t> sr = comm.allreduce({cssize - sent0_, crsize - recv0_}, Comm::SUM);
+    if (sr[0] || sr[1]) {
+      const double mb = 1024.0 * 1024.0;
+      if (comm.rank() == 0) out(fmt("%s Comm = %.3g Mb send, %.3g Mb recv\n", heading, sr[0] / mb, sr[1] / mb));
+      if (m.set.verbosity == 2) {
+        m.histo((cssize - sent0_) / mb, "  Send (Mb):");
+        m.histo((crsize - recv0_) / mb, "  Recv (Mb):");
+      }
+    }
+  }
+
+  MapReduce* mr_;
+  const char* name_;
+  double began_ = 0;
+  int64_t sent0_ = 0, recv0_ = 0;
+  std::optional<hbm::OpCap> cap_;
+};
+
+namespace {
+// collate and scrunch run their inner ops silently: the caller's verbosity and
+// timer come back on scope exit, also when an inner op throws
+struct Quiet {
+  explicit Quiet(Settings& s) : set_(s), verbosity_(s.verbosity), timer_(s.timer) { s.verbosity = s.timer = 0; }
+  ~Quiet() {
+    set_.verbosity = verbosity_;
+    set_.timer = timer_;
+  }
+  Settings& set_;
+  const int verbosity_, timer_;
+};
+}  // namespace
+
 // ====================================================================== lifecycle
 
 MapReduce::MapReduce(CommPtr comm) : comm_(std::move(comm)) {
@@ -323,42 +451,6 @@ MapReduce::~MapReduce() {
   drop_disk();
   guard::unregister_mr(this);
   instances_now--;
-}
-
-// every op's entry: fault injection point, and data spilled to host (spill()
-// or spill-on-OOM) comes back to HBM before the op touches it
-void MapReduce::enter(const char* op, bool ooc_ok, bool parts_ok, bool kmv_parts_ok) {
-  guard::fault_point(op, comm_->rank());
-  if (!parts_ok) flatten();
-  if (!kmv_parts_ok) flatten_kmv();
-  if (guard::alloc_guard_active()) {  // an overrun found at the end of an earlier op fails the next one
-    static size_t raised = 0;
-    const auto reps = guard::guard_reports();
-    if (reps.size() > raised) {
-      const guard::GuardReport& r = reps[raised];
-      raised = reps.size();
-      throw std::runtime_error("mrhip guard: out-of-bounds device write into a " + std::to_string(r.size) +
-                               "-byte block allocated in " + r.alloc_op + ", detected " + r.found_op);
-    }
-  }
-  if (!started_) {
-    started_ = true;
-    // minpage (reference allocate(), src/mapreduce.cpp:3318-3357): pages
-    // claimed up front; here the caching allocator's pool is grown by
-    // minpage x memsize once, so the first ops do not pay for hipMalloc
-    if (set.minpage > 0 && device().is_cuda()) {
-      at::Tensor t = at::empty({(int64_t)set.minpage * block_bytes()}, at::TensorOptions().device(device()).dtype(at::kByte));
-    }
-  }
-  ensure_resident();
-  // a group-by index outlives its KV only until the next op sees the KV changed
-  if (grouped_ && (!kv || !grouped_->describes(*kv))) grouped_.reset();
-  const bool on_host = (kv && !kv->device().is_cuda()) || (kmv && !kmv->keys.device().is_cuda());
-  if (!device().is_cuda() || !on_host) return;
-  // an op with an out-of-core path leaves host-resident data larger than the
-  // HBM budget where it is and streams it; every other op brings it back
-  if (ooc_ok && needs_ooc(data_bytes(), budget(), 2.0)) return;
-  unspill();
 }
 
 // A map/reduce builder of an MR with an HBM or host budget is bounded: its
@@ -544,15 +636,6 @@ void MapReduce::need_kmv(const char* what) const {
   if (!kmv) fail(std::string("Cannot ") + what + " without KeyMultiValue");
 }
 
-void MapReduce::start() {
-  if (set.timer) {
-    if (set.timer == 1) comm_->barrier();
-    t0_ = Comm::wtime();
-  }
-  cs0_ = cssize.load();
-  cr0_ = crsize.load();
-}
-
 void MapReduce::histo(double v, const char* heading) const {
   std::vector<double> vals = comm_->allgather_f64(v);
   double ave = 0, mx = vals[0], mn = vals[0];
@@ -576,42 +659,6 @@ void MapReduce::histo(double v, const char* heading) const {
   }
 }
 
-// per-op stats (reference :3112-3179)
-void MapReduce::stats(const char* heading, int which) {
-  if (guard::check_enabled()) {
-    if (kv) guard::check_kv(*kv, heading);
-    for (const KMV& m : kmv_parts()) guard::check_kmv(m, heading);
-  }
-  const int64_t b = data_bytes();
-  msize = b;
-  if (b > msizemax) msizemax = b;
-  if (set.timer) {
-    if (set.timer == 1) {
-      comm_->barrier();
-      if (comm_->rank() == 0) out(fmt("%s time (secs) = %g\n", heading, Comm::wtime() - t0_));
-    } else if (set.timer == 2) {
-      histo(Comm::wtime() - t0_, (std::string(heading) + " time (secs) =").c_str());
-    }
-  }
-  if (set.verbosity == 0) return;
-  if (which == 0) {
-    if (comm_->rank() == 0) out(std::string(heading) + " KV = ");
-    kv_stats(set.verbosity);
-  } else {
-    if (comm_->rank() == 0) out(std::string(heading) + " KMV = ");
-    kmv_stats(set.verbosity);
-  }
-  std::vector<int64_t> sr = comm_->allreduce({cssize - cs0_, crsize - cr0_}, Comm::SUM);
-  if (sr[0] || sr[1]) {
-    const double mb = 1024.0 * 1024.0;
-    if (comm_->rank() == 0) out(fmt("%s Comm = %.3g Mb send, %.3g Mb recv\n", heading, sr[0] / mb, sr[1] / mb));
-    if (set.verbosity == 2) {
-      histo((cssize - cs0_) / mb, "  Send (Mb):");
-      histo((crsize - cr0_) / mb, "  Recv (Mb):");
-    }
-  }
-}
-
 void MapReduce::note_shuffle(const ShuffleStats& st) {
   cssize += st.send_bytes;
   crsize += st.recv_bytes;
@@ -624,15 +671,12 @@ uint64_t MapReduce::add(MapReduce& other) {  // :348-374
   // O(appended): other's pairs become parts of this KV where they are (the
   // reference reopens only the last page, src/keyvalue.cpp:185-209); nothing
   // this object holds is copied
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, true);
+  Op frame(this, __func__, true, true);
   need_kv("add");
   other.ensure_resident();
   if (!other.kv) fail("MapReduce passed to add() does not have KeyValue pairs");
   for (const KV& p : other.kv_parts()) append_part(p);
-  stats("Add", 0);
-  return count(kv_rows());
+  return frame.kv_done("Add");
 }
 
 void MapReduce::open(int addflag) {  // :1648-1664
@@ -649,6 +693,7 @@ KeyValue& MapReduce::kv_open() {
 
 uint64_t MapReduce::close() {  // :658-672
   if (!open_) fail("Cannot close MapReduce that is not open");
+  Op frame(this);
   KV n = open_->finish();
   std::shared_ptr<GroupIndex> g = open_->take_group();
   open_.reset();
@@ -661,8 +706,7 @@ uint64_t MapReduce::close() {  // :658-672
     kv = n;
     grouped_ = g;
   }
-  stats("Close", 0);
-  return count(kv_rows());
+  return frame.kv_done("Close");
 }
 
 // ====================================================================== map
@@ -687,7 +731,16 @@ std::vector<int> MapReduce::my_tasks(int nmap) {  // :1102-1225
   return t;
 }
 
-uint64_t MapReduce::finish_map(KeyValue& kvb, int addflag, const char* heading) {
+// self: the KV a map over this object's own pairs read (map_mr / map_mr_batch with src == this)
+uint64_t MapReduce::finish_map(Op& frame, KeyValue& kvb, int addflag, const KV* self) {
+  if (self && addflag) {
+    KV n = kvb.finish();
+    note_spool(kvb);
+    kv = *self;
+    append_part(n);
+    drop_kmv();
+    return frame.kv_done("Map");
+  }
   // the builder's chunks / spool pieces become the KV's parts (no concatenation)
   std::vector<KV> n = kvb.finish_parts();
   note_spool(kvb);
@@ -699,19 +752,17 @@ uint64_t MapReduce::finish_map(KeyValue& kvb, int addflag, const char* heading) 
     grouped_ = g;
   }
   drop_kmv();
-  stats(heading, 0);
-  return count(kv_rows());
+  return frame.kv_done("Map");
 }
 
 uint64_t MapReduce::map(int nmap, const MapTaskFn& fn, int addflag) {  // :1044-1051
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag);
-  enter(__func__);
+  frame.enter();
   KeyValue kvb(device());
   bound(kvb);
   for (int t : my_tasks(nmap)) fn(t, kvb);
-  return finish_map(kvb, addflag);
+  return finish_map(frame, kvb, addflag);
 }
 
 std::vector<std::string> MapReduce::find_files(const Comm& comm, const std::vector<std::string>& files,
@@ -741,10 +792,9 @@ std::vector<std::string> MapReduce::find_files(const Comm& comm, const std::vect
 
 uint64_t MapReduce::map_file(const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
                              const MapFileFn& fn, int addflag) {  // :1060-1092
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag);
-  enter(__func__);
+  frame.enter();
   auto fl = find_files(*comm_, files, selfflag, recurse, readflag);
   mapfilecount = (int)fl.size();
   KeyValue kvb(device());
@@ -754,7 +804,7 @@ uint64_t MapReduce::map_file(const std::vector<std::string>& files, int selfflag
   } else {
     for (int t : my_tasks((int)fl.size())) fn(t, fl[t].c_str(), kvb);
   }
-  return finish_map(kvb, addflag);
+  return finish_map(frame, kvb, addflag);
 }
 
 uint64_t MapReduce::map_file_char(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
@@ -774,10 +824,9 @@ uint64_t MapReduce::map_file_str(int nmap, const std::vector<std::string>& files
 uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
                                int readflag, const std::string& sep, bool is_char, int delta, const MapChunkFn& fn,
                                int addflag) {
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag);
-  enter(__func__);
+  frame.enter();
   auto fl = find_files(*comm_, files, selfflag, recurse, readflag);
   mapfilecount = (int)fl.size();
   const int nfile = (int)fl.size();
@@ -849,14 +898,13 @@ uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, 
     buf[s1] = '\0';  // the reference NUL-terminates the chunk for strtok-style callbacks
     fn(t, &buf[s0], (int)(s1 - s0), kvb);
   }
-  return finish_map(kvb, addflag);
+  return finish_map(frame, kvb, addflag);
 }
 
 uint64_t MapReduce::map_mr(MapReduce& src, const MapKVFn& fn, int addflag) {  // :1560-1642
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag, &src);
-  enter(__func__);
+  frame.enter();
   src.ensure_resident();
   src.flatten();
   src.flatten_kmv();
@@ -868,23 +916,13 @@ uint64_t MapReduce::map_mr(MapReduce& src, const MapKVFn& fn, int addflag) {  //
   KeyValue kvb(device());
   bound(kvb);
   for (int64_t i = 0; i < s.n; ++i) fn((uint64_t)i, k.at(i), (int)k.len(i), v.at(i), (int)v.len(i), kvb);
-  if (&src == this && addflag) {
-    KV n = kvb.finish();
-    note_spool(kvb);
-    kv = s;
-    append_part(n);
-    drop_kmv();
-    stats("Map", 0);
-    return count(kv_rows());
-  }
-  return finish_map(kvb, addflag);
+  return finish_map(frame, kvb, addflag, &src == this ? &s : nullptr);
 }
 
 uint64_t MapReduce::map_mr_batch(MapReduce& src, const MapBatchFn& fn, int addflag) {
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag, &src);
-  enter(__func__);
+  frame.enter();
   src.ensure_resident();
   src.flatten();
   src.flatten_kmv();
@@ -893,24 +931,13 @@ uint64_t MapReduce::map_mr_batch(MapReduce& src, const MapBatchFn& fn, int addfl
   KeyValue kvb(device());
   bound(kvb);
   fn(s, kvb);
-  if (&src == this && addflag) {
-    KV n = kvb.finish();
-    note_spool(kvb);
-    kv = s;
-    append_part(n);
-    drop_kmv();
-    stats("Map", 0);
-    return count(kv_rows());
-  }
-  return finish_map(kvb, addflag);
+  return finish_map(frame, kvb, addflag, &src == this ? &s : nullptr);
 }
 
 // ====================================================================== shuffle
 
 uint64_t MapReduce::aggregate(const HashFn& hash) {  // :385-563
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, !comm_->distributed());  // one rank: nothing moves, appended parts stay
+  Op frame(this, __func__, true, !comm_->distributed());  // one rank: nothing moves, appended parts stay
   need_kv("aggregate");
   if (comm_->distributed() && ooc_shuffle()) {
     // larger than the budget: budget-sized chunks in lock-step, received into
@@ -931,8 +958,7 @@ uint64_t MapReduce::aggregate(const HashFn& hash) {  // :385-563
     }
     note_shuffle(st);
   }
-  stats("Aggregate", 0);
-  return count(kv_rows());
+  return frame.kv_done("Aggregate");
 }
 
 // owner rank of every pair by a user hash (MR-MPI's hash callback, run on the
@@ -959,9 +985,7 @@ bool MapReduce::ooc_shuffle() const {
 }
 
 uint64_t MapReduce::aggregate_dest(const at::Tensor& dest) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, !comm_->distributed());
+  Op frame(this, __func__, true, !comm_->distributed());
   need_kv("aggregate");
   if (comm_->distributed()) {
     ShuffleStats st;
@@ -981,24 +1005,18 @@ uint64_t MapReduce::aggregate_dest(const at::Tensor& dest) {
     }
     note_shuffle(st);
   }
-  stats("Aggregate", 0);
-  return count(kv_rows());
+  return frame.kv_done("Aggregate");
 }
 
 uint64_t MapReduce::broadcast(int root) {  // :569-623
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
+  Op frame(this, __func__);
   need_kv("broadcast");
   if (comm_->distributed()) kv = mrh::broadcast(*kv, root, *comm_);
-  stats("Broadcast", 0);
-  return count(kv->n);
+  return frame.kv_done("Broadcast");
 }
 
 uint64_t MapReduce::gather(int nprocs) {  // :893-1036
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);
+  Op frame(this, __func__, true);
   need_kv("gather");
   if (nprocs < 1 || nprocs > comm_->size()) fail("Invalid proc count for gather");
   if (comm_->distributed() && (nprocs < comm_->size() || comm_->uses_rccl())) {
@@ -1013,18 +1031,31 @@ uint64_t MapReduce::gather(int nprocs) {  // :893-1036
     }
     note_shuffle(st);
   }
-  stats("Gather", 0);
-  return count(kv->n);
+  return frame.kv_done("Gather");
 }
 
 // ====================================================================== group-by
 
+namespace {
+// the groups of `kv` from the index that grouped it as it arrived (grouped =
+// 1), or, after a 64-bit hash collision, from an exact regroup (grouped = 2)
+KMV finish_grouped(GroupIndex& g, const KV& kv, ConvertStats* cs) {
+  KMV m;
+  if (g.finish(&m, cs)) {
+    cs->grouped = 1;
+    return m;
+  }
+  *cs = ConvertStats();
+  m = mrh::convert(kv, cs, 64);
+  cs->grouped = 2;
+  return m;
+}
+}  // namespace
+
 uint64_t MapReduce::convert() { return convert_prehashed(at::Tensor()); }
 
 uint64_t MapReduce::convert_prehashed(const at::Tensor& prehash) {  // :861-886
-  start();
-  OpTrace tr_("convert", this);
-  enter("convert", true, !prehash.defined());
+  Op frame(this, "convert", true, !prehash.defined());
   need_kv("convert");
   last_convert = ConvertStats();
   if (needs_ooc(data_bytes(), budget(), 4.0)) {
@@ -1035,15 +1066,7 @@ uint64_t MapReduce::convert_prehashed(const at::Tensor& prehash) {  // :861-886
     note_ooc("Convert", os);
   } else if (grouped_ && grouped_->describes(*kv) && !prehash.defined()) {
     // grouped while the map produced it: only the two short sorts are left
-    KMV m;
-    if (grouped_->finish(&m, &last_convert)) {
-      kmv = std::move(m);
-      last_convert.grouped = 1;
-    } else {
-      last_convert = ConvertStats();
-      kmv = mrh::convert(*kv, &last_convert, 64);  // a 64-bit hash collision: exact regroup
-      last_convert.grouped = 2;
-    }
+    kmv = finish_grouped(*grouped_, *kv, &last_convert);
   } else if (!prehash.defined() && (!kv_tail_.empty() || kv->kfixed())) {
     // narrow pairs, possibly in parts: grouped with every part read in place
     // and released once packed (packed pairs), else concatenated once for
@@ -1075,16 +1098,13 @@ uint64_t MapReduce::convert_prehashed(const at::Tensor& prehash) {  // :861-886
   grouped_.reset();
   kv.reset();
   kv_tail_.clear();
-  stats("Convert", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Convert");
 }
 
 uint64_t MapReduce::collate(const HashFn& hash) {  // :710-738
-  start();
-  OpTrace tr_(__func__, this);
   // with a budget: aggregate and convert stream out-of-core data themselves;
   // on one rank they also read appended parts in place
-  enter(__func__, true, !comm_->distributed());
+  Op frame(this, __func__, true, !comm_->distributed());
   need_kv("collate");
   // pipelined collate: the hash-partition exchange hands every received round
   // to a GroupIndex, which groups it on the compute stream while the next
@@ -1109,29 +1129,18 @@ uint64_t MapReduce::collate(const HashFn& hash) {  // :710-738
       kmv = mrh::convert(*kv, &last_convert);
     } else {
       kv = g.kv();
-      KMV m;
-      if (g.finish(&m, &last_convert)) {
-        kmv = std::move(m);
-        last_convert.grouped = 1;
-      } else {
-        last_convert = ConvertStats();
-        kmv = mrh::convert(*kv, &last_convert, 64);
-        last_convert.grouped = 2;
-      }
+      kmv = finish_grouped(g, *kv, &last_convert);
     }
     kv.reset();
     grouped_.reset();
-    stats("Collate", 1);
-    return count(kmv_keys());
+    return frame.kmv_done("Collate");
   }
-  const int v = set.verbosity, t = set.timer;
-  set.verbosity = set.timer = 0;
-  aggregate(hash);
-  convert();
-  set.verbosity = v;
-  set.timer = t;
-  stats("Collate", 1);
-  return count(kmv_keys());
+  {
+    Quiet quiet(set);
+    aggregate(hash);
+    convert();
+  }
+  return frame.kmv_done("Collate");
 }
 
 // compress's local group-by: out of core (hash-partitioned spools) past the budget
@@ -1147,42 +1156,40 @@ KMV MapReduce::local_groups(const char* heading) {
 }
 
 uint64_t MapReduce::clone() {  // :631-652
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);  // one value per key: a host-resident KV is cloned where it lives
+  Op frame(this, __func__, true);  // one value per key: a host-resident KV is cloned where it lives
   need_kv("clone");
   kmv = oom_retry(this, device(), my_proc(), "clone", [&] { return mrh::clone(*kv); });
   kv.reset();
-  stats("Clone", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Clone");
 }
 
 uint64_t MapReduce::collapse(const char* key, int kb) {  // :681-702
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
+  Op frame(this, __func__);
   need_kv("collapse");
   kmv = mrh::collapse(*kv, std::string(key, (size_t)kb));
   kv.reset();
-  stats("Collapse", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Collapse");
 }
 
 uint64_t MapReduce::scrunch(int nprocs, const char* key, int kb) {  // :2075-2095
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
-  const int v = set.verbosity, t = set.timer;
-  set.verbosity = set.timer = 0;
-  gather(nprocs);
-  collapse(key, kb);
-  set.verbosity = v;
-  set.timer = t;
-  stats("Scrunch", 1);
-  return count(kmv_keys());
+  Op frame(this, __func__);
+  {
+    Quiet quiet(set);
+    gather(nprocs);
+    collapse(key, kb);
+  }
+  return frame.kmv_done("Scrunch");
 }
 
 // ====================================================================== reduce family
+
+namespace {
+// the value type of the builtin reducers when the caller names none
+const std::string& builtin_dtype(const std::string& dtype) {
+  static const std::string int32 = "int32";
+  return dtype.empty() ? int32 : dtype;
+}
+}  // namespace
 
 ExchangeOpts MapReduce::xopts() const {
   ExchangeOpts o;
@@ -1257,27 +1264,44 @@ int MapReduce::multivalue_block(int iblock, char** mv, int** valuebytes) {
   return (int)(j1 - j0);
 }
 
-uint64_t MapReduce::reduce(const ReduceFn& fn) {  // :1769-1867
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, false, true);  // host callbacks read host-resident data (every KMV part) in place
-  need_kmv("reduce");
+// The body of the host / batch reduce and compress ops: `fn(groups, builder)`
+// emits into a bounded builder whose parts become the KV. It sees each KMV of
+// `src` whole or, with `pieces`, as key ranges whose values fit the budget,
+// in HBM one at a time (each a KMV of its own, in key order).
+template <typename Fn>
+void MapReduce::emit_kv(const std::vector<KMV>& src, bool pieces, const char* heading, Fn&& fn) {
   KeyValue kvb(device());
   bound(kvb);
-  for (const KMV& m : kmv_parts())
-    run_host_kmv(m, [&](char* k, int kb, char* mv, int nv, int* vb) { fn(k, kb, mv, nv, vb, kvb); });
+  if (pieces) {
+    OocStats os;
+    for (const KMV& m : src)
+      ooc_for_each_kmv_piece(m, ooc_env(), device(), [&](const KMV& piece) { fn(piece, kvb); }, &os);
+    note_ooc(heading, os);
+  } else {
+    for (const KMV& m : src) fn(m, kvb);
+  }
   set_kv_parts(kvb.finish_parts());
   note_spool(kvb);
+}
+// the host callback form: every group where it lies, never in pieces
+void MapReduce::emit_kv(const std::vector<KMV>& src, const ReduceFn& fn) {
+  emit_kv(src, false, nullptr, [&](const KMV& m, KeyValue& kvb) {
+    run_host_kmv(m, [&](char* k, int kb, char* mv, int nv, int* vb) { fn(k, kb, mv, nv, vb, kvb); });
+  });
+}
+
+uint64_t MapReduce::reduce(const ReduceFn& fn) {  // :1769-1867
+  Op frame(this, __func__, true, false, true);  // host callbacks read host-resident data (every KMV part) in place
+  need_kmv("reduce");
+  emit_kv(kmv_parts(), fn);
   drop_kmv();
-  stats("Reduce", 0);
-  return count(kv_rows());
+  return frame.kv_done("Reduce");
 }
 
 uint64_t MapReduce::reduce_builtin(const std::string& op, const std::string& dtype) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, false, kmv_part_count() > 1);
+  Op frame(this, __func__, true, false, kmv_part_count() > 1);
   need_kmv("reduce");
+  const std::string& dt = builtin_dtype(dtype);
   if (kmv_part_count() > 1 && budget() <= 0) {
     // parts left by an out-of-core convert, but no budget now (it was lowered
     // to 0 = unlimited): each part reduced whole on the engine device (the
@@ -1286,86 +1310,48 @@ uint64_t MapReduce::reduce_builtin(const std::string& op, const std::string& dty
     for (const KMV& m : kmv_parts()) {
       const KMV dm = m.seg.device() == device() ? m : kmv_to(m, device(), false);
       outs.push_back(oom_retry(this, device(), my_proc(), "reduce_builtin",
-                               [&] { return mrh::reduce_builtin(dm, op, dtype.empty() ? "int32" : dtype); }));
+                               [&] { return mrh::reduce_builtin(dm, op, dt); }));
     }
     set_kv_parts(std::move(outs));
   } else if (kmv_part_count() > 1 || needs_ooc(kmv->nbytes(), budget(), 2.0)) {
     // values stream through HBM in budget-sized key ranges, part by part
     OocStats os;
     std::vector<KV> outs;
-    for (const KMV& m : kmv_parts()) outs.push_back(ooc_reduce_builtin(m, op, dtype.empty() ? "int32" : dtype, ooc_env(), device(), &os));
+    for (const KMV& m : kmv_parts()) outs.push_back(ooc_reduce_builtin(m, op, dt, ooc_env(), device(), &os));
     set_kv_parts(std::move(outs));
     note_ooc("Reduce", os);
   } else {
     kv = oom_retry(this, device(), my_proc(), "reduce_builtin",
-                   [&] { return mrh::reduce_builtin(*kmv, op, dtype.empty() ? "int32" : dtype); });
+                   [&] { return mrh::reduce_builtin(*kmv, op, dt); });
   }
   drop_kmv();
-  stats("Reduce", 0);
-  return count(kv_rows());
+  return frame.kv_done("Reduce");
 }
 
 uint64_t MapReduce::reduce_batch(const ReduceBatchFn& fn) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, false, kmv_part_count() > 1);
+  Op frame(this, __func__, true, false, kmv_part_count() > 1);
   need_kmv("reduce");
-  KeyValue kvb(device());
-  bound(kvb);
-  if (kmv_part_count() > 1 || needs_ooc(kmv->nbytes(), budget(), 2.0)) {
-    // key ranges whose values fit the budget go to HBM one at a time, part
-    // by part; the batch callback sees each as a KMV of its own (in key order)
-    OocStats os;
-    for (const KMV& m : kmv_parts())
-      ooc_for_each_kmv_piece(m, ooc_env(), device(), [&](const KMV& piece) { fn(piece, kvb); }, &os);
-    note_ooc("Reduce", os);
-  } else {
-    fn(*kmv, kvb);
-  }
-  set_kv_parts(kvb.finish_parts());
-  note_spool(kvb);
+  emit_kv(kmv_parts(), kmv_part_count() > 1 || needs_ooc(kmv->nbytes(), budget(), 2.0), "Reduce", fn);
   drop_kmv();
-  stats("Reduce", 0);
-  return count(kv_rows());
+  return frame.kv_done("Reduce");
 }
 
 uint64_t MapReduce::compress(const ReduceFn& fn) {  // :749-851
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);  // host callbacks read the (host-resident) groups in place
+  Op frame(this, __func__, true);  // host callbacks read the (host-resident) groups in place
   need_kv("compress");
-  KMV m = local_groups("Compress");
-  KeyValue kvb(device());
-  bound(kvb);
-  run_host_kmv(m, [&](char* k, int kb, char* mv, int nv, int* vb) { fn(k, kb, mv, nv, vb, kvb); });
-  set_kv_parts(kvb.finish_parts());
-  note_spool(kvb);
-  stats("Compress", 0);
-  return count(kv_rows());
+  emit_kv({local_groups("Compress")}, fn);
+  return frame.kv_done("Compress");
 }
 
 // compress with a batch callback: the local groups of this rank's pairs as one
 // KMV (pieces of it when they exceed the budget), fn emits tensors — the
 // combiner form of reduce_batch (reference compress, src/mapreduce.cpp:749-851)
 uint64_t MapReduce::compress_batch(const ReduceBatchFn& fn) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);
+  Op frame(this, __func__, true);
   need_kv("compress");
-  KMV m = local_groups("Compress");
-  KeyValue kvb(device());
-  bound(kvb);
-  if (needs_ooc(m.nbytes(), budget(), 2.0) || (device().is_cuda() && !m.seg.is_cuda())) {
-    OocStats os;
-    ooc_for_each_kmv_piece(m, ooc_env(), device(), [&](const KMV& piece) { fn(piece, kvb); }, &os);
-    note_ooc("Compress", os);
-  } else {
-    fn(m, kvb);
-  }
-  set_kv_parts(kvb.finish_parts());
-  note_spool(kvb);
-  stats("Compress", 0);
-  return count(kv_rows());
+  const KMV m = local_groups("Compress");
+  emit_kv({m}, needs_ooc(m.nbytes(), budget(), 2.0) || (device().is_cuda() && !m.seg.is_cuda()), "Compress", fn);
+  return frame.kv_done("Compress");
 }
 
 // ====================================================================== device functors
@@ -1446,6 +1432,19 @@ uint64_t MapReduce::reduce_device(const std::string& code) {
 }
 
 namespace {
+// what the sorts of one column report: the op name (trace, fault points,
+// errors) and the stats heading
+const char* sort_name(bool by_value) { return by_value ? "sort_values" : "sort_keys"; }
+const char* sort_heading(bool by_value) { return by_value ? "Sort_values" : "Sort_keys"; }
+
+// the values of a KMV reordered by an int32 permutation (within each key's
+// segment): fixed-width rows, or variable-width ones with their new offsets
+void permute_values(KMV& m, const at::Tensor& perm) {
+  at::Tensor noff;
+  m.vdata = gather_rows(m.vdata, m.voff, m.vw, perm, m.vw < 0 ? &noff : nullptr);
+  if (m.vw < 0) m.voff = noff;
+}
+
 // the pairs sorted by a device sort functor over one column, stable:
 // mr_sortkey -> radix sort of its 64-bit keys; mr_compare -> the merge sort
 KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_value, at::Device dev,
@@ -1466,30 +1465,25 @@ KV sort_by_functor(const KV& kv_in, const std::string& code, int bits, bool by_v
 }
 }  // namespace
 
-// sort_keys_device / sort_values_device: op = the caller's name, what / heading as need_kv / stats print them
-uint64_t MapReduce::sort_column_device(const char* op, const char* what, const char* heading, bool by_value,
-                                       const std::string& code, int bits) {
-  start();
-  OpTrace tr_(op, this);
-  enter(op);
-  need_kv(what);
+// sort_keys_device / sort_values_device: the trace and the fault points see
+// the op's own name, need_kv and the heading those of sort_keys / sort_values
+uint64_t MapReduce::sort_column_device(bool by_value, const std::string& code, int bits) {
+  Op frame(this, by_value ? "sort_values_device" : "sort_keys_device");
+  need_kv(sort_name(by_value));
   kv = sort_by_functor(*kv, code, bits, by_value, device(), devfn::args_of(dev_args_));
-  stats(heading, 0);
-  return count(kv->n);
+  return frame.kv_done(sort_heading(by_value));
 }
 
 uint64_t MapReduce::sort_keys_device(const std::string& code, int bits) {
-  return sort_column_device(__func__, "sort_keys", "Sort_keys", false, code, bits);
+  return sort_column_device(false, code, bits);
 }
 
 uint64_t MapReduce::sort_values_device(const std::string& code, int bits) {
-  return sort_column_device(__func__, "sort_values", "Sort_values", true, code, bits);
+  return sort_column_device(true, code, bits);
 }
 
 uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
-  start();
-  OpTrace tr_("sort_multivalues", this);
-  enter("sort_multivalues");
+  Op frame(this, "sort_multivalues");
   need_kmv("sort_multivalues");
   const devfn::Kind kind = devfn::sort_kind_of(code);
   const at::Device dev = device();
@@ -1513,13 +1507,10 @@ uint64_t MapReduce::sort_multivalues_device(const std::string& code, int bits) {
       (void)p2;
       perm = perm2;
     }
-    at::Tensor noff;
-    m.vdata = gather_rows(m.vdata, m.voff, m.vw, perm, m.vw < 0 ? &noff : nullptr);
-    if (m.vw < 0) m.voff = noff;
+    permute_values(m, perm);
     kmv = m;
   }
-  stats("Sort_multivalues", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Sort_multivalues");
 }
 
 uint64_t MapReduce::compress_device(const std::string& code) {
@@ -1531,12 +1522,11 @@ uint64_t MapReduce::compress_device(const std::string& code) {
 // goes through HBM in budget-sized pieces, every item once, a pair's index
 // its index on this rank.
 uint64_t MapReduce::scan_device(const std::string& code) {
-  start();
-  OpTrace tr_(__func__, this);
+  Op frame(this, __func__, Op::Deferred());
   const at::Device dev = device();
   if (!dev.is_cuda()) fail("mrhip: device functors run on a GPU MapReduce (device cuda)");
   const devfn::Args bound = devfn::args_of(dev_args_);
-  enter(__func__, true, false, true);
+  frame.enter(true, false, true);
   if (kv) {
     if (kv->n && !kv->device().is_cuda()) {
       OocStats os;
@@ -1546,8 +1536,7 @@ uint64_t MapReduce::scan_device(const std::string& code) {
     } else if (kv->n) {
       devfn::scan_pairs(*kv, 0, code, dev, bound);
     }
-    stats("Scan", 0);
-    return count(kv->n);
+    return frame.kv_done("Scan");
   }
   need_kmv("scan");
   OocStats os;
@@ -1563,48 +1552,39 @@ uint64_t MapReduce::scan_device(const std::string& code) {
     }
   }
   if (pieces) note_ooc("Scan", os);
-  stats("Scan", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Scan");
 }
 
 uint64_t MapReduce::compress_builtin(const std::string& op, const std::string& dtype) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);
+  Op frame(this, __func__, true);
   need_kv("compress");
+  const std::string& dt = builtin_dtype(dtype);
   KMV m = local_groups("Compress");
   if (needs_ooc(m.nbytes(), budget(), 2.0)) {
     OocStats os;
-    kv = ooc_reduce_builtin(m, op, dtype.empty() ? "int32" : dtype, ooc_env(), device(), &os);
+    kv = ooc_reduce_builtin(m, op, dt, ooc_env(), device(), &os);
     note_ooc("Compress", os);
   } else {
-    kv = mrh::reduce_builtin(m, op, dtype.empty() ? "int32" : dtype);
+    kv = mrh::reduce_builtin(m, op, dt);
   }
-  stats("Compress", 0);
-  return count(kv->n);
+  return frame.kv_done("Compress");
 }
 
 uint64_t MapReduce::scan_kv(const ScanKVFn& fn) {  // :1933-1976
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);  // host callbacks read host-resident data in place
+  Op frame(this, __func__, true);  // host callbacks read host-resident data in place
   need_kv("scan");
   HostCol k = host_col(kv->kdata, kv->koff, kv->kw), v = host_col(kv->vdata, kv->voff, kv->vw);
   align_col(k, kv->n, set.keyalign, nullptr, 0, set.zeropage);
   align_col(v, kv->n, set.valuealign, nullptr, 0, set.zeropage);
   for (int64_t i = 0; i < kv->n; ++i) fn(k.at(i), (int)k.len(i), v.at(i), (int)v.len(i));
-  stats("Scan", 0);
-  return count(kv->n);
+  return frame.kv_done("Scan");
 }
 
 uint64_t MapReduce::scan_kmv(const ScanKMVFn& fn) {  // :1984-2065
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true, false, true);  // host callbacks read host-resident data (every KMV part) in place
+  Op frame(this, __func__, true, false, true);  // host callbacks read host-resident data (every KMV part) in place
   need_kmv("scan");
   for (const KMV& m : kmv_parts()) run_host_kmv(m, fn);
-  stats("Scan", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Scan");
 }
 
 // ====================================================================== sorting
@@ -1622,67 +1602,41 @@ at::Tensor host_perm(const at::Tensor& data, const at::Tensor& off, int w, int64
 }
 }  // namespace
 
-uint64_t MapReduce::sort_keys(int flag) {  // :2102-2126
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);
-  need_kv("sort_keys");
+// sort_keys / sort_values (reference :2102-2203): one column, by a type flag or a host comparator
+uint64_t MapReduce::sort_column(bool by_value, int flag) {
+  const char* name = sort_name(by_value);
+  Op frame(this, name, true);
+  need_kv(name);
   if (needs_ooc(kv->nbytes(), budget(), 4.0)) {
     OocStats os;
-    kv = ooc_sort(*kv, flag, false, ooc_env(), device(), &os);  // sample sort over host spools
-    note_ooc("Sort_keys", os);
+    kv = ooc_sort(*kv, flag, by_value, ooc_env(), device(), &os);  // sample sort over host spools
+    note_ooc(sort_heading(by_value), os);
   } else {
-    kv = oom_retry(this, device(), my_proc(), "sort_keys", [&] { return sort_kv(*kv, flag, false); });
+    kv = oom_retry(this, device(), my_proc(), name, [&] { return sort_kv(*kv, flag, by_value); });
   }
-  stats("Sort_keys", 0);
-  return count(kv->n);
+  return frame.kv_done(sort_heading(by_value));
 }
-uint64_t MapReduce::sort_keys(const CompareFn& fn) {  // :2134-2149
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
-  need_kv("sort_keys");
-  if (kv->n > 1) kv = mrh::gather(*kv, host_perm(kv->kdata, kv->koff, kv->kw, kv->n, fn, device()));
-  stats("Sort_keys", 0);
-  return count(kv->n);
+uint64_t MapReduce::sort_column(bool by_value, const CompareFn& fn) {
+  Op frame(this, sort_name(by_value));
+  need_kv(sort_name(by_value));
+  if (kv->n > 1)
+    kv = mrh::gather(*kv, host_perm(by_value ? kv->vdata : kv->kdata, by_value ? kv->voff : kv->koff,
+                                    by_value ? kv->vw : kv->kw, kv->n, fn, device()));
+  return frame.kv_done(sort_heading(by_value));
 }
-uint64_t MapReduce::sort_values(int flag) {  // :2156-2180
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__, true);
-  need_kv("sort_values");
-  if (needs_ooc(kv->nbytes(), budget(), 4.0)) {
-    OocStats os;
-    kv = ooc_sort(*kv, flag, true, ooc_env(), device(), &os);
-    note_ooc("Sort_values", os);
-  } else {
-    kv = oom_retry(this, device(), my_proc(), "sort_values", [&] { return sort_kv(*kv, flag, true); });
-  }
-  stats("Sort_values", 0);
-  return count(kv->n);
-}
-uint64_t MapReduce::sort_values(const CompareFn& fn) {  // :2188-2203
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
-  need_kv("sort_values");
-  if (kv->n > 1) kv = mrh::gather(*kv, host_perm(kv->vdata, kv->voff, kv->vw, kv->n, fn, device()));
-  stats("Sort_values", 0);
-  return count(kv->n);
-}
+uint64_t MapReduce::sort_keys(int flag) { return sort_column(false, flag); }
+uint64_t MapReduce::sort_keys(const CompareFn& fn) { return sort_column(false, fn); }
+uint64_t MapReduce::sort_values(int flag) { return sort_column(true, flag); }
+uint64_t MapReduce::sort_values(const CompareFn& fn) { return sort_column(true, fn); }
+
 uint64_t MapReduce::sort_multivalues(int flag) {  // :2210-2352
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
+  Op frame(this, __func__);
   need_kmv("sort_multivalues");
   kmv = mrh::sort_multivalues(*kmv, flag);
-  stats("Sort_multivalues", 1);
-  return count(kmv_keys());
+  return frame.kmv_done("Sort_multivalues");
 }
 uint64_t MapReduce::sort_multivalues(const CompareFn& fn) {
-  start();
-  OpTrace tr_(__func__, this);
-  enter(__func__);
+  Op frame(this, __func__);
   need_kmv("sort_multivalues");
   KMV& m = *kmv;
   HostCol v = host_col(m.vdata, m.voff, m.vw);
@@ -1694,12 +1648,8 @@ uint64_t MapReduce::sort_multivalues(const CompareFn& fn) {
     std::stable_sort(p.begin() + s[i], p.begin() + s[i + 1], [&](int32_t a, int32_t b) {
       return fn(v.at(a), (int)v.len(a), v.at(b), (int)v.len(b)) < 0;
     });
-  at::Tensor perm = at::from_blob(p.data(), {m.nval}, at::TensorOptions().dtype(at::kInt)).clone().to(device());
-  at::Tensor noff;
-  m.vdata = gather_rows(m.vdata, m.voff, m.vw, perm, m.vw < 0 ? &noff : nullptr);
-  if (m.vw < 0) m.voff = noff;
-  stats("Sort_multivalues", 1);
-  return count(m.nkey);
+  permute_values(m, at::from_blob(p.data(), {m.nval}, at::TensorOptions().dtype(at::kInt)).clone().to(device()));
+  return frame.kmv_done("Sort_multivalues");
 }
 
 // ====================================================================== print
@@ -2018,7 +1968,7 @@ int64_t MapReduce::read_file(const std::string& p) {
 // The third memory tier (HBM -> pinned host -> disk): the data goes to a
 // per-rank file named like the reference's out-of-core files
 // (fpath/mrmpi.<kv|kmv>.<instance>.<counter>.<rank>, src/mapreduce.cpp:3187-3205)
-// and comes back on the MR's next op (ensure_resident, called from enter()).
+// and comes back on the MR's next op (ensure_resident, called from the op frame's enter()).
 void MapReduce::spill_disk() {
   flatten();
   flatten_kmv();

@@ -245,11 +245,18 @@ class MapReduce {
   static std::vector<std::string> find_files(const Comm& comm, const std::vector<std::string>& files, int selfflag,
                                              int recurse, int readflag);
 
+
+  // the tiers and names an out-of-core op of this MR may use
+  OocEnv ooc_env() const;
+  // HBM budget of this object's data in bytes (0 = unlimited)
+  int64_t budget() const;
+  // memsize-sized pages a local KV/KMV of `bytes` spans (reference kv_stats
+  // "N pages"; the out-of-core ops record their partition count too)
+  int64_t pages(int64_t bytes) const { return std::max<int64_t>({int64_t(1), (bytes + block_bytes() - 1) / block_bytes(), pages_}); }
+
  private:
-  void start();
-  // parts_ok: the op reads the appended KV parts itself (else they are
-  // flattened); kmv_parts_ok: the same for the KMV's parts
-  void enter(const char* op, bool ooc_ok = false, bool parts_ok = false, bool kmv_parts_ok = false);
+  // the frame every op runs in (mapreduce.cpp): start state, trace, entry, finish
+  class Op;
   void set_kmv_parts(std::vector<KMV> parts);
   void drop_kmv();
   // append `b` as a part: device parts past the HBM budget go through a
@@ -262,10 +269,6 @@ class MapReduce {
   int64_t data_bytes() const;
   void bound(KeyValue& b);
   KV concat_parts(const std::vector<KV>& parts);
- public:
-  // the tiers and names an out-of-core op of this MR may use
-  OocEnv ooc_env() const;
- private:
   void note_spool(const KeyValue& b);
   void note_ooc(const char* op, const OocStats& st);
   // out-of-core helpers: a shuffle past the budget, a user hash's owner ranks
@@ -273,27 +276,25 @@ class MapReduce {
   bool ooc_shuffle() const;
   at::Tensor host_dest(const HashFn& hash) const;
   KMV local_groups(const char* heading);
-  void stats(const char* heading, int which);
+  // the KV becomes what `fn(part, builder)` emits into a bounded builder for
+  // every KMV of `src`: each whole, or (pieces) in budget-sized key ranges
+  template <typename Fn>
+  void emit_kv(const std::vector<KMV>& src, bool pieces, const char* heading, Fn&& fn);
+  void emit_kv(const std::vector<KMV>& src, const ReduceFn& fn);
   void need_kv(const char* what) const;
   void need_kmv(const char* what) const;
-  uint64_t sort_column_device(const char* op, const char* what, const char* heading, bool by_value,
-                              const std::string& code, int bits);
+  uint64_t sort_column(bool by_value, int flag);
+  uint64_t sort_column(bool by_value, const CompareFn& fn);
+  uint64_t sort_column_device(bool by_value, const std::string& code, int bits);
   void note_shuffle(const ShuffleStats& st);
   uint64_t count(int64_t n) const { return (uint64_t)comm_->allreduce(n, Comm::SUM); }
   std::vector<int> my_tasks(int nmap);
-  uint64_t finish_map(KeyValue& kvb, int addflag, const char* heading = "Map");
+  uint64_t finish_map(Op& frame, KeyValue& kvb, int addflag, const KV* self = nullptr);
   uint64_t map_chunks(int nmap, const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
                       const std::string& sep, bool is_char, int delta, const MapChunkFn& fn, int addflag);
   void run_host_kmv(const KMV& kmv, const std::function<void(char*, int, char*, int, int*)>& fn);
   void histo(double v, const char* heading) const;
   int64_t block_bytes() const;
- public:
-  // HBM budget of this object's data in bytes (0 = unlimited)
-  int64_t budget() const;
-  // memsize-sized pages a local KV/KMV of `bytes` spans (reference kv_stats
-  // "N pages"; the out-of-core ops record their partition count too)
-  int64_t pages(int64_t bytes) const { return std::max<int64_t>({int64_t(1), (bytes + block_bytes() - 1) / block_bytes(), pages_}); }
- private:
   // shuffle options from the settings
   ExchangeOpts xopts() const;
 
@@ -315,8 +316,6 @@ class MapReduce {
   std::unique_ptr<KeyValue> open_;
   std::vector<at::Tensor> dev_args_;  // set_device_args
   int open_add_ = 0;
-  double t0_ = 0;
-  int64_t cs0_ = 0, cr0_ = 0;
   int instance_me_ = 0;
   // multi-block state of the key currently handed to a host callback
   struct Blocks {
