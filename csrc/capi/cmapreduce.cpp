@@ -220,6 +220,18 @@ uint64_t MR_map_device(void* p, void* src, const char* code, int addflag) {
 uint64_t MR_map_device_tasks(void* p, uint64_t ntask, const char* code, int addflag) {
   return guard([&] { return M(p)->map_device_tasks((int64_t)ntask, code, addflag); }, (uint64_t)0);
 }
+uint64_t MR_map_file_char_device(void* p, int nmap, int nstr, char** s, int recurse, int readflag, char sep, int delta,
+                                 const char* code, int addflag) {
+  return guard(
+      [&] { return M(p)->map_file_char_device(nmap, strs(nstr, s), 0, recurse, readflag, sep, delta, code, addflag); },
+      (uint64_t)0);
+}
+uint64_t MR_map_file_str_device(void* p, int nmap, int nstr, char** s, int recurse, int readflag, char* sep, int delta,
+                                const char* code, int addflag) {
+  return guard(
+      [&] { return M(p)->map_file_str_device(nmap, strs(nstr, s), 0, recurse, readflag, sep, delta, code, addflag); },
+      (uint64_t)0);
+}
 uint64_t MR_reduce_device(void* p, const char* code) {
   return guard([&] { return M(p)->reduce_device(code); }, (uint64_t)0);
 }

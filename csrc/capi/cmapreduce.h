@@ -83,6 +83,14 @@ uint64_t MR_reduce_builtin(void *MRptr, const char *op, const char *dtype);
    compiled at run time for the GPU; a GPU MapReduce only */
 uint64_t MR_map_device(void *MRptr, void *MRptr2, const char *code, int addflag);
 uint64_t MR_map_device_tasks(void *MRptr, uint64_t ntask, const char *code, int addflag);
+/* MR_map_file_char / MR_map_file_str with a device functor: every chunk is cut into records in HBM and
+   each record goes through mr_map in place. sepchar terminates a record; sepstr (1 to 16 bytes) starts
+   one. key = 8 bytes (long long: the file's index in the expanded file list), value = the record,
+   index = the byte offset of the record's first byte in its file */
+uint64_t MR_map_file_char_device(void *MRptr, int nmap, int nstr, char **strings, int recurse, int readflag,
+                                 char sepchar, int delta, const char *code, int addflag);
+uint64_t MR_map_file_str_device(void *MRptr, int nmap, int nstr, char **strings, int recurse, int readflag,
+                                char *sepstr, int delta, const char *code, int addflag);
 uint64_t MR_reduce_device(void *MRptr, const char *code);
 uint64_t MR_compress_device(void *MRptr, const char *code);
 /* stable sort by a device sort functor: mr_sortkey (key -> 64-bit key in the wanted order, radix sort

@@ -500,6 +500,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("map_device_tasks", &MR::map_device_tasks, py::arg("ntask"), py::arg("code"), py::arg("addflag") = 0,
            py::call_guard<py::gil_scoped_release>())
+      .def("map_file_char_device",
+           [](MR& r, int nmap, std::vector<std::string> files, int self, int rec, int rd, const std::string& sep,
+              int delta, const std::string& code, int add) {
+             return r.map_file_char_device(nmap, files, self, rec, rd, sep.empty() ? '\n' : sep[0], delta, code, add);
+           },
+           py::arg("nmap"), py::arg("files"), py::arg("selfflag"), py::arg("recurse"), py::arg("readflag"),
+           py::arg("sepchar"), py::arg("delta"), py::arg("code"), py::arg("addflag") = 0,
+           py::call_guard<py::gil_scoped_release>())
+      .def("map_file_str_device", &MR::map_file_str_device, py::arg("nmap"), py::arg("files"), py::arg("selfflag"),
+           py::arg("recurse"), py::arg("readflag"), py::arg("sepstr"), py::arg("delta"), py::arg("code"),
+           py::arg("addflag") = 0, py::call_guard<py::gil_scoped_release>())
       .def("reduce_device", &MR::reduce_device, py::call_guard<py::gil_scoped_release>())
       .def("compress_device", &MR::compress_device, py::call_guard<py::gil_scoped_release>())
       .def("sort_keys_device", &MR::sort_keys_device, py::arg("code"), py::arg("bits") = 64,
@@ -754,7 +765,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::call_guard<py::gil_scoped_release>());
   m.def("map_urls", &map_urls);
   m.def("kmeans_map", &kmeans_map);
+  m.def("url_starts", [](const at::Tensor& text, int64_t n) {
+    auto [starts, nurl] = url_starts(text, n);
+    return py::make_tuple(starts.narrow(0, 0, nurl), nurl);
+  });
   m.def("map_words", &map_words);
+  m.def(
+      "split_records",
+      [](const at::Tensor& text, int64_t n, int64_t nread, const std::string& sep, bool is_char) {
+        auto [off, nrec] = split_records(text, n, nread, sep, is_char);
+        return py::make_tuple(off, nrec);
+      },
+      py::arg("text"), py::arg("n"), py::arg("nread"), py::arg("sep"), py::arg("is_char"));
   m.def("map_rmat", [](int64_t ne, int nl, double a, double b, double c, double d, double f, uint64_t seed,
                        uint64_t first, const std::string& dev) {
     return map_rmat(ne, nl, a, b, c, d, f, seed, first, at::Device(dev));
@@ -979,6 +1001,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("device_functor_check", &devfn::compile_check, py::arg("code"), py::arg("reduce"),
         py::call_guard<py::gil_scoped_release>());
   m.def("device_functor_source", &devfn::full_source, py::arg("code"), py::arg("reduce"));
+  m.def("device_text_check", &devfn::compile_check_text, py::arg("code"), py::call_guard<py::gil_scoped_release>());
+  // records [a, b) of a text in HBM through mr_map (devfn.h map_records); one process
+  m.def(
+      "device_map_records",
+      [](const at::Tensor& text, const at::Tensor& off, int64_t nrec, int64_t trim, int64_t file, int64_t base,
+         const std::string& code, const std::vector<at::Tensor>& args) {
+        return devfn::map_records(text, off, nrec, trim, file, base, code, text.device(), 0, -1, devfn::args_of(args));
+      },
+      py::arg("text"), py::arg("off"), py::arg("nrec"), py::arg("trim"), py::arg("file"), py::arg("base"),
+      py::arg("code"), py::arg("args") = std::vector<at::Tensor>(), py::call_guard<py::gil_scoped_release>());
   m.def("device_sortkey_check", &devfn::compile_check_sortkey, py::arg("code"),
         py::call_guard<py::gil_scoped_release>());
   m.def("device_compare_check", &devfn::compile_check_compare, py::arg("code"),

@@ -76,6 +76,9 @@ struct KindRow {
 //   mrd_cmp_merge     (col, const i64* sid, i64 n, const u32* src, u32* dst, i64 W, Args)
 //   mrd_scan          (items, i64 base, i64 n, MutArgs)
 //   mrd_hash          (col, i64 n, int P, int* dest, Args)
+// MapText has mrd_count / mrd_write of its own: the same parameters with
+//   records = const u8* text, const i64* off, i64 trim, i64 file, i64 base
+// in the place of items
 const KindRow kKinds[] = {
     {"mrd_map.hip", "MRD_REDUCE", 0, text::kEmitKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
     {"mrd_reduce.hip", "MRD_REDUCE", 1, text::kEmitKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
@@ -87,6 +90,7 @@ const KindRow kKinds[] = {
      "the comparator functor's"},
     {"mrd_scan.hip", "MRD_SCAN_KMV", 0, text::kScanKernel, {"mrd_scan"}, "the scan functor's"},
     {"mrd_hash.hip", nullptr, 0, text::kHashKernel, {"mrd_hash"}, "the partitioner functor's"},
+    {"mrd_map_text.hip", nullptr, 0, text::kTextKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
 };
 const KindRow& row_of(Kind kind) { return kKinds[(int)kind]; }
 
@@ -223,7 +227,15 @@ void launch_items(hipFunction_t f, int64_t threads, hipStream_t s, const Items& 
   launch(f, grid_of(threads), s, it.k.d, it.k.off, it.k.w, it.v.d, it.v.off, it.v.w, it.seg, rest...);
 }
 
-KV run(const Items& it, const std::string& code, Kind kind, at::Device dev, const Args& bound) {
+// The two-pass emit over `n` items from `first` on: head(f, rest...) launches
+// kernel f over them with the kind's leading parameters (its items) in front
+// of rest
+template <class Head>
+KV run_emit(int64_t first, int64_t n, const Head& head, const std::string& code, Kind kind, at::Device dev,
+            const Args& bound) {
+  struct {
+    int64_t first, n;
+  } it{first, n};
   KV out;
   out.kw = out.vw = -1;
   if (it.n <= 0) {
@@ -240,7 +252,7 @@ KV run(const Items& it, const std::string& code, Kind kind, at::Device dev, cons
   if (hipMemcpyAsync(wid.data_ptr(), w0, sizeof(w0), hipMemcpyHostToDevice, s) != hipSuccess)
     throw std::runtime_error("mrhip: hipMemcpyAsync failed");
   auto count = [&](int bytes) {
-    launch_items(m.fn[kCount], it.n, s, it, it.first, it.n, P0<int64_t>(cnt), P0<int64_t>(wid), bytes, bound);
+    head(m.fn[kCount], it.first, it.n, P0<int64_t>(cnt), P0<int64_t>(wid), bytes, bound);
   };
   count(0);
   // the record widths first: uniform widths need only the record scan (the
@@ -272,12 +284,18 @@ KV run(const Items& it, const std::string& code, Kind kind, at::Device dev, cons
   if (nout && ovw >= 0) out.vw = (int)ovw;
   else out.voff = at::empty({nout + 1}, opt(dev, at::kLong));
   if (nout)
-    launch_items(m.fn[kWrite], it.n, s, it, it.first, it.n, P0<int64_t>(pr), P0<int64_t>(pk), P0<int64_t>(pv), okw,
-                 ovw, P0<uint8_t>(out.kdata), P0<int64_t>(out.koff), P0<uint8_t>(out.vdata), P0<int64_t>(out.voff),
-                 bound);
+    head(m.fn[kWrite], it.first, it.n, P0<int64_t>(pr), P0<int64_t>(pk), P0<int64_t>(pv), okw, ovw,
+         P0<uint8_t>(out.kdata), P0<int64_t>(out.koff), P0<uint8_t>(out.vdata), P0<int64_t>(out.voff), bound);
   if (out.koff.defined()) k::fill_i64(P0<int64_t>(out.koff) + nout, 1, tot[1], s);
   if (out.voff.defined()) k::fill_i64(P0<int64_t>(out.voff) + nout, 1, tot[2], s);
   return out;
+}
+
+KV run(const Items& it, const std::string& code, Kind kind, at::Device dev, const Args& bound) {
+  hipStream_t s = at::hip::getCurrentHIPStream();
+  return run_emit(
+      it.first, it.n, [&](hipFunction_t f, const auto&... rest) { launch_items(f, it.n, s, it, rest...); }, code, kind,
+      dev, bound);
 }
 
 // fold tier: accumulators per chunk of values, merged per key, then mr_finish per key
@@ -321,6 +339,7 @@ int64_t run_scan(const Items& it, const std::string& code, bool kmv, at::Device 
 std::string full_source(const std::string& code, bool reduce) { return source_of(code, kind_of(code, reduce)); }
 
 int64_t compile_check(const std::string& code, bool reduce) { return check(code, kind_of(code, reduce)); }
+int64_t compile_check_text(const std::string& code) { return check(code, Kind::MapText); }
 int64_t compile_check_sortkey(const std::string& code) { return check(code, Kind::SortKey); }
 int64_t compile_check_compare(const std::string& code) { return check(code, Kind::Compare); }
 int64_t compile_check_scan(const std::string& code, bool kmv) { return check(code, Kind::Scan, kmv); }
@@ -362,6 +381,22 @@ KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev, 
   it.first = first;
   it.n = n;
   return run(it, code, Kind::Map, dev, bound);
+}
+
+KV map_records(const at::Tensor& text, const at::Tensor& off, int64_t nrec, int64_t trim, int64_t file, int64_t base,
+               const std::string& code, at::Device dev, int64_t a, int64_t b, const Args& bound) {
+  need_gpu(dev);
+  if (b < 0 || b > nrec) b = nrec;
+  a = std::max<int64_t>(a, 0);
+  if (b > a && (!text.is_cuda() || !off.is_cuda() || off.numel() < nrec + 1))
+    throw std::runtime_error("mrhip: map_records needs the text and its nrec + 1 record offsets in HBM");
+  hipStream_t s = at::hip::getCurrentHIPStream();
+  const uint8_t* t = P0<uint8_t>(text);
+  const int64_t* o = P0<int64_t>(off);
+  return run_emit(
+      a, b - a,
+      [&](hipFunction_t f, const auto&... rest) { launch(f, grid_of(b - a), s, t, o, trim, file, base, rest...); }, code,
+      Kind::MapText, dev, bound);
 }
 
 KV reduce_groups(const KMV& m, const std::string& code, at::Device dev, const Args& bound) {

@@ -51,8 +51,9 @@
 namespace mrh {
 namespace devfn {
 // the functor kinds: mr_map; mr_reduce per key; the fold form (mr_init / mr_add
-// / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan; mr_hash
-enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan, Hash };
+// / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan; mr_hash; mr_map
+// over the records of a text
+enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan, Hash, MapText };
 // the bound buffers as every functor kernel takes them (layout of mrd::Args /
 // mrd::MutArgs in the prelude); slots past n are {nullptr, 0}
 constexpr int kMaxArgs = 8;
@@ -72,6 +73,17 @@ KV map_pairs(const KV& kv, const std::string& code, at::Device dev, int64_t a = 
              const Args& args = Args{});
 // map over n tasks (no input): mr_map(empty, empty, task, out)
 KV map_tasks(int64_t first, int64_t n, const std::string& code, at::Device dev, const Args& args = Args{});
+// map over file records: the same mr_map over records [a, b) (b < 0: to the
+// end) of a text in HBM as split_records (kv.h) cut it: record i is
+// text[off[i], off[i + 1] - trim), read in place. key = 8 bytes, `file` (a
+// long long: the file's index in the expanded file list); value = the record;
+// index = base + off[i], the byte offset of the record's first byte in its
+// file when base is the file offset of text[0]. A kind of its own
+// (Kind::MapText): a new text, separator or split never recompiles.
+KV map_records(const at::Tensor& text, const at::Tensor& off, int64_t nrec, int64_t trim, int64_t file, int64_t base,
+               const std::string& code, at::Device dev, int64_t a = 0, int64_t b = -1, const Args& args = Args{});
+// compile only, as the record map compiles it; the code object size in bytes
+int64_t compile_check_text(const std::string& code);
 // reduce: every key of m through mr_reduce
 KV reduce_groups(const KMV& m, const std::string& code, at::Device dev, const Args& args = Args{});
 // compile only (syntax / type errors come back with the compiler log);

@@ -536,6 +536,93 @@ mrd_hash(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, int P, i
 }
 )MRD";
 
+// mr_map over the records of a text in HBM (devfn.h map_records): record i is
+// text[off[i], off[i + 1] - trim), read in place; key = the 8 bytes of `file`,
+// index = base + off[i]. The two passes of kEmitKernels with records in the
+// place of pairs (a source of its own: the other kinds' sources stay as they are).
+const char kTextKernels[] = R"MRD(
+// ---- mrd record-map kernels ----
+namespace mrd {
+MRD_SHIM(map, (class E), (Bytes k, Bytes v, i64 t, E& e), (k, v, t, e))
+__device__ inline void run_record(const u8* text, const i64* off, i64 trim, i64 file, i64 base, i64 i, Emit& e,
+                                  const Args& g) {
+  const i64 a = off[i], b = off[i + 1] - trim;
+  call_map(Bytes{(const u8*)&file, 8}, Bytes{text + a, b > a ? b - a : 0}, base + a, e, g, 0);
+}
+}  // namespace mrd
+extern "C" __global__ __launch_bounds__(256) void
+mrd_count(const mrd::u8* text, const mrd::i64* off, mrd::i64 trim, mrd::i64 file, mrd::i64 base, mrd::i64 first,
+          mrd::i64 n, mrd::i64* cnt, mrd::u64* wid, int bytes, mrd::Args args) {
+  mrd::u64 kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0;
+  for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
+    mrd::Emit e{false, 0, 0, 0, ~0ull, 0, ~0ull, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+    mrd::run_record(text, off, trim, file, base, first + i, e, args);
+    cnt[i] = e.nrec;
+    if (bytes) {
+      cnt[n + i] = e.kb;
+      cnt[2 * n + i] = e.vb;
+    }
+    kmin = e.kmin < kmin ? e.kmin : kmin;
+    kmax = e.kmax > kmax ? e.kmax : kmax;
+    vmin = e.vmin < vmin ? e.vmin : vmin;
+    vmax = e.vmax > vmax ? e.vmax : vmax;
+  }
+  // the record widths: wave, then block min / max, one set of atomics per block
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const mrd::u64 a = __shfl_xor(kmin, d, 64), b = __shfl_xor(kmax, d, 64);
+    const mrd::u64 c = __shfl_xor(vmin, d, 64), e = __shfl_xor(vmax, d, 64);
+    kmin = a < kmin ? a : kmin;
+    kmax = b > kmax ? b : kmax;
+    vmin = c < vmin ? c : vmin;
+    vmax = e > vmax ? e : vmax;
+  }
+  __shared__ mrd::u64 red[4][4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[w][0] = kmin;
+    red[w][1] = kmax;
+    red[w][2] = vmin;
+    red[w][3] = vmax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; ++i) {
+      kmin = red[i][0] < kmin ? red[i][0] : kmin;
+      kmax = red[i][1] > kmax ? red[i][1] : kmax;
+      vmin = red[i][2] < vmin ? red[i][2] : vmin;
+      vmax = red[i][3] > vmax ? red[i][3] : vmax;
+    }
+    if (kmax || kmin != ~0ull) {
+      atomicMin(wid + 0, kmin);
+      atomicMax(wid + 1, kmax);
+      atomicMin(wid + 2, vmin);
+      atomicMax(wid + 3, vmax);
+    }
+  }
+}
+extern "C" __global__ __launch_bounds__(256) void
+mrd_write(const mrd::u8* text, const mrd::i64* off, mrd::i64 trim, mrd::i64 file, mrd::i64 base, mrd::i64 first,
+          mrd::i64 n, const mrd::i64* pr, const mrd::i64* pk, const mrd::i64* pv, mrd::i64 okw, mrd::i64 ovw,
+          mrd::u8* okd, mrd::i64* okoff, mrd::u8* ovd, mrd::i64* ovoff, mrd::Args args) {
+  for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
+    const mrd::i64 r = pr[i];
+    if (pr[i + 1] == r) continue;
+    const mrd::i64 r1 = pr[i + 1];
+    const mrd::i64 k0 = okw >= 0 ? r * okw : pk[i], v0 = ovw >= 0 ? r * ovw : pv[i];
+    const mrd::i64 k1 = okw >= 0 ? r1 * okw : pk[i + 1], v1 = ovw >= 0 ? r1 * ovw : pv[i + 1];
+    mrd::Emit e{true, 0, 0, 0, 0, 0, 0, 0, okd + k0, okw >= 0 ? nullptr : okoff + r, ovd + v0,
+                ovw >= 0 ? nullptr : ovoff + r, r1 - r, k1 - k0, v1 - v0};
+    mrd::run_record(text, off, trim, file, base, first + i, e, args);
+    const mrd::i64 nw = e.nrec < r1 - r ? e.nrec : r1 - r;
+    for (mrd::i64 j = 0; j < nw; ++j) {  // offsets relative to the item -> absolute
+      if (okw < 0) okoff[r + j] += k0;
+      if (ovw < 0) ovoff[r + j] += v0;
+    }
+  }
+}
+)MRD";
+
 }  // namespace text
 }  // namespace devfn
 }  // namespace mrh

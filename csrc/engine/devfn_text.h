@@ -15,6 +15,7 @@ extern const char kSortKeyKernel[];   // mr_sortkey
 extern const char kCompareKernels[];  // mr_compare (MRD_CMP_T rows per tile)
 extern const char kScanKernel[];      // mr_scan (MRD_SCAN_KMV 0 / 1)
 extern const char kHashKernel[];      // mr_hash
+extern const char kTextKernels[];     // mr_map over the records of a text
 }  // namespace text
 }  // namespace devfn
 }  // namespace mrh

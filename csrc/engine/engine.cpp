@@ -1807,6 +1807,22 @@ KMV sort_multivalues(const KMV& kmv, int flag) {
 
 // ====================================================================== text & graph maps
 
+// the first byte of every URL of a device text (count, scan, emit): (starts, at least one entry; their number)
+std::pair<at::Tensor, int64_t> url_starts(const at::Tensor& text, int64_t n) {
+  const at::Device dev = text.device();
+  if (!dev.is_cuda()) fail("url_starts: the text must be on the GPU");
+  if (text.numel() < n + 32) fail("url_starts: text buffer must be padded by >= 32 bytes");
+  auto s = cur_stream();
+  int64_t nt = k::url_num_tiles(n);
+  at::Tensor cnt = at::empty({std::max<int64_t>(nt, 1)}, opt(dev, at::kInt));
+  k::url_count(P0<uint8_t>(text), n, P0<uint32_t>(cnt), s);
+  at::Tensor toff = scan_u32(cnt.narrow(0, 0, nt));
+  int64_t nurl = (int64_t)(uint32_t)toff[nt].item<int32_t>();
+  at::Tensor starts = at::empty({std::max<int64_t>(nurl, 1)}, opt(dev, at::kLong));
+  k::url_emit_starts(P0<uint8_t>(text), n, P0<uint32_t>(toff), P0<int64_t>(starts), s);
+  return {starts, nurl};
+}
+
 KV map_urls(const at::Tensor& text, int64_t n, int32_t doc_id) {
   const at::Device dev = text.device();
   if (text.numel() < n + 32) fail("map_urls: text buffer must be padded by >= 32 bytes");
@@ -1815,13 +1831,7 @@ KV map_urls(const at::Tensor& text, int64_t n, int32_t doc_id) {
   kv.vw = 4;
   if (dev.is_cuda()) {
     auto s = cur_stream();
-    int64_t nt = k::url_num_tiles(n);
-    at::Tensor cnt = at::empty({std::max<int64_t>(nt, 1)}, opt(dev, at::kInt));
-    k::url_count(P0<uint8_t>(text), n, P0<uint32_t>(cnt), s);
-    at::Tensor toff = scan_u32(cnt.narrow(0, 0, nt));
-    int64_t nurl = (int64_t)(uint32_t)toff[nt].item<int32_t>();
-    at::Tensor starts = at::empty({std::max<int64_t>(nurl, 1)}, opt(dev, at::kLong));
-    k::url_emit_starts(P0<uint8_t>(text), n, P0<uint32_t>(toff), P0<int64_t>(starts), s);
+    auto [starts, nurl] = url_starts(text, n);
     at::Tensor klen = at::empty({std::max<int64_t>(nurl, 1)}, opt(dev, at::kInt));
     k::url_lengths(P0<uint8_t>(text), n, P0<int64_t>(starts), nurl, P0<int32_t>(klen), s);
     kv.koff = exclusive_scan(klen.narrow(0, 0, nurl));
@@ -1851,6 +1861,59 @@ KV map_urls(const at::Tensor& text, int64_t n, int32_t doc_id) {
   kv.kdata = at::from_blob(kd.data(), {(int64_t)kd.size()}, opt(at::kCPU, at::kByte)).clone();
   kv.vdata = at::full({kv.n}, doc_id, opt(at::kCPU, at::kInt)).view(at::kByte);
   return kv;
+}
+
+// the records of text[0, n) between the occurrences of sep (kv.h). Both
+// devices build off the same way: `base` leading entries written here (char
+// mode: off[0] = 0; string mode: off[0] = 0 unless an occurrence starts at
+// byte 0), one entry per occurrence (its position + trim), then the end.
+std::pair<at::Tensor, int64_t> split_records(const at::Tensor& text, int64_t n, int64_t nread, const std::string& sep,
+                                             bool is_char) {
+  const int64_t L = (int64_t)sep.size();
+  if (L < 1 || L > 16)
+    fail("split_records: a separator of " + std::to_string(L) + " bytes; it must have 1 to 16 bytes");
+  if (is_char && L != 1) fail("split_records: a terminator (char mode) is 1 byte, " + std::to_string(L) + " given");
+  if (text.scalar_type() != at::kByte || !text.is_contiguous()) fail("split_records: text must be contiguous uint8");
+  if (n < 0 || nread < n) fail("split_records: need 0 <= n <= nread");
+  if (text.numel() < nread + 32) fail("split_records: text buffer must be padded by >= 32 bytes");
+  const at::Device dev = text.device();
+  const int64_t trim = is_char ? 1 : 0;
+  if (n == 0) return {at::zeros({1}, opt(dev, at::kLong)), 0};
+  const uint8_t* sp = reinterpret_cast<const uint8_t*>(sep.data());
+  if (dev.is_cuda()) {
+    if (reinterpret_cast<uintptr_t>(text.data_ptr()) & 15) fail("split_records: text must be 16-byte aligned");
+    auto s = cur_stream();
+    const int64_t nt = k::url_num_tiles(n);
+    at::Tensor cnt = at::empty({nt + 1}, opt(dev, at::kInt));  // + the flag
+    k::sep_count(P0<uint8_t>(text), n, nread, sp, (int)L, is_char, P0<uint32_t>(cnt), P0<uint32_t>(cnt) + nt, s);
+    at::Tensor toff = exclusive_scan(cnt.narrow(0, 0, nt));  // i64 [nt + 1]
+    int64_t nocc = 0;
+    uint32_t flag = 0;
+    read_small(s, {{P0<int64_t>(toff) + nt, &nocc, 8}, {P0<uint32_t>(cnt) + nt, &flag, 4}});
+    const int64_t base = is_char ? 1 : (int64_t)flag;
+    const int64_t nrec = nocc + (int64_t)flag;
+    at::Tensor off = at::empty({nrec + 1}, opt(dev, at::kLong));
+    if (base) k::fill_i64(P0<int64_t>(off), 1, 0, s);
+    if (nocc) k::sep_emit(P0<uint8_t>(text), n, nread, sp, (int)L, P0<int64_t>(toff), trim, P0<int64_t>(off) + base, s);
+    if (!is_char || flag) k::fill_i64(P0<int64_t>(off) + nrec, 1, n + trim, s);
+    return {off, nrec};
+  }
+  const uint8_t* t = P0<uint8_t>(text);
+  std::vector<int64_t> off;
+  for (int64_t p = 0; p < n && p + L <= nread; ++p) {
+    if (memcmp(t + p, sp, (size_t)L) != 0) continue;
+    if (!is_char && p > 0 && off.empty()) off.push_back(0);
+    off.push_back(p + trim);
+  }
+  if (is_char) {
+    off.insert(off.begin(), 0);
+    if (off.back() < n) off.push_back(n + trim);  // an unterminated last record
+  } else {
+    if (off.empty()) off.push_back(0);
+    off.push_back(n);
+  }
+  const int64_t nrec = (int64_t)off.size() - 1;
+  return {at::from_blob(off.data(), {nrec + 1}, opt(at::kCPU, at::kLong)).clone(), nrec};
 }
 
 static inline bool is_ws(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\f' || c == '\r' || c == 0; }

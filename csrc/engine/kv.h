@@ -212,8 +212,22 @@ KV broadcast(const KV& kv, int root, const Comm& comm);
 // ------------------------------------------------------------------ text / graph maps
 // InvertedIndex map over one text buffer (padded by >= 32 bytes): KV(url+NUL, int32 doc)
 KV map_urls(const at::Tensor& text, int64_t n, int32_t doc_id);
+// its first step alone, on the GPU: the position after every `<a href="` (int64, at least one entry) and their number
+std::pair<at::Tensor, int64_t> url_starts(const at::Tensor& text, int64_t n);
 // wordfreq map: KV(word+NUL, NULL)
 KV map_words(const at::Tensor& text, int64_t n);
+// The records of text[0, n) (uint8, on either device, >= 32 readable bytes past
+// nread) between the occurrences of sep (1 to 16 bytes): positions p < n with
+// text[p, p + L) == sep and p + L <= nread (nread >= n: the look-ahead that
+// may complete a match), overlapping ones included; padding never matches.
+// is_char (L == 1): sep terminates a record — [0, q0), [q0 + 1, q1), ..., a
+// last [q_last + 1, n) only if non-empty; empty records between adjacent
+// terminators are kept. Otherwise sep starts a record — [0, m0) if non-empty,
+// [m_i, m_i+1), [m_last, n); no occurrence: the whole text. Returns (off int64
+// [nrec + 1] on the text's device, nrec): record i is text[off[i], off[i + 1]
+// - trim), trim = 1 in char mode (the terminator) and 0 otherwise.
+std::pair<at::Tensor, int64_t> split_records(const at::Tensor& text, int64_t n, int64_t nread, const std::string& sep,
+                                             bool is_char);
 // R-MAT: KV(EDGE{u64,u64}, NULL)
 KV map_rmat(int64_t nedges, int nlevels, double a, double b, double c, double d, double fraction,
             uint64_t seed, uint64_t first_edge, at::Device dev);

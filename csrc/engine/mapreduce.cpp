@@ -27,6 +27,7 @@
 #include <optional>
 #include <sstream>
 #include <stdexcept>
+#include <string_view>
 
 namespace mrh {
 
@@ -827,6 +828,30 @@ uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, 
   Op frame(this, __func__, Op::Deferred());
   drop_for_map(addflag);
   frame.enter();
+  KeyValue kvb(device());
+  bound(kvb);
+  std::string buf;
+  for_chunks(
+      nmap, files, selfflag, recurse, readflag, sep, is_char, delta,
+      [&](int64_t bytes) {
+        buf.assign((size_t)bytes, '\0');
+        return &buf[0];
+      },
+      [&](const FileChunk& c) {
+        c.buf[c.s1] = '\0';  // the reference NUL-terminates the chunk for strtok-style callbacks
+        fn(c.task, c.buf + c.s0, (int)(c.s1 - c.s0), kvb);
+      });
+  return finish_map(frame, kvb, addflag);
+}
+
+// The chunks of map_chunks, for the host callbacks and the device functors
+// alike: the file list, the plan of ~nmap byte ranges, this rank's tasks, each
+// task's read (rs bytes from st into room(rs + 1), zero-filled past what was
+// read) and its boundaries s0 / s1 repaired on the separator
+void MapReduce::for_chunks(int nmap, const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
+                           const std::string& sep, bool is_char, int delta,
+                           const std::function<char*(int64_t)>& room,
+                           const std::function<void(const FileChunk&)>& fn) {
   auto fl = find_files(*comm_, files, selfflag, recurse, readflag);
   mapfilecount = (int)fl.size();
   const int nfile = (int)fl.size();
@@ -863,8 +888,6 @@ uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, 
     for (int i = 0; i < nfile; ++i)
       for (int j = 0; j < tpf[i]; ++j) plan.push_back({i, j, tpf[i], sizes[i]});
   }
-  KeyValue kvb(device());
-  bound(kvb);
   std::vector<int> tasks;
   if (selfflag) {
     tasks.resize(plan.size());
@@ -872,18 +895,19 @@ uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, 
   } else {
     tasks = my_tasks((int)plan.size());
   }
-  std::string buf;
   for (int t : tasks) {
     const ChunkTask& c = plan[t];
     const int64_t st = (int64_t)c.itask * c.fsize / c.ntask, nx = (int64_t)(c.itask + 1) * c.fsize / c.ntask;
     const int64_t rs = std::min<int64_t>(nx - st + delta, c.fsize - st);
-    buf.assign((size_t)rs + 1, '\0');
+    char* b = room(rs + 1);
     std::FILE* f = std::fopen(fl[c.ifile].c_str(), "rb");
     if (!f) fail("Could not open file " + fl[c.ifile]);
     std::fseek(f, (long)st, SEEK_SET);
-    size_t got = std::fread(&buf[0], 1, (size_t)rs, f);
+    size_t got = std::fread(b, 1, (size_t)rs, f);
     std::fclose(f);
+    std::memset(b + got, 0, (size_t)(rs + 1) - got);
     rsize += (int64_t)got;
+    const std::string_view buf(b, (size_t)rs + 1);
     int64_t s0 = 0, s1 = (int64_t)got;
     if (c.itask > 0) {
       size_t p = buf.find(sep, 0);
@@ -895,10 +919,8 @@ uint64_t MapReduce::map_chunks(int nmap, const std::vector<std::string>& files, 
       if (p == std::string::npos || (int64_t)p >= (int64_t)got) fail("Could not find file separator within delta");
       s1 = (int64_t)p + (is_char ? 1 : 0);
     }
-    buf[s1] = '\0';  // the reference NUL-terminates the chunk for strtok-style callbacks
-    fn(t, &buf[s0], (int)(s1 - s0), kvb);
+    fn(FileChunk{t, c.ifile, st, (int64_t)got, s0, s1, b});
   }
-  return finish_map(frame, kvb, addflag);
 }
 
 uint64_t MapReduce::map_mr(MapReduce& src, const MapKVFn& fn, int addflag) {  // :1560-1642
@@ -1425,6 +1447,64 @@ uint64_t MapReduce::map_device_tasks(int64_t ntask, const std::string& code, int
         }
       },
       addflag);
+}
+
+uint64_t MapReduce::map_file_char_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
+                                         int readflag, char sepchar, int delta, const std::string& code, int addflag) {
+  return map_chunks_device(nmap, files, selfflag, recurse, readflag, std::string(1, sepchar), true, delta, code,
+                           addflag);
+}
+
+uint64_t MapReduce::map_file_str_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
+                                        int readflag, const std::string& sepstr, int delta, const std::string& code,
+                                        int addflag) {
+  return map_chunks_device(nmap, files, selfflag, recurse, readflag, sepstr, false, delta, code, addflag);
+}
+
+// map_chunks with a device functor over the chunk's records: every task's
+// chunk is read into pinned host memory, copied to HBM once, cut into records
+// there (split_records) and mapped in place (devfn::map_records). The records
+// do not depend on where the chunks were cut: a chunk boundary is an
+// occurrence of the separator, and every occurrence bounds a record.
+uint64_t MapReduce::map_chunks_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
+                                      int readflag, const std::string& sep, bool is_char, int delta,
+                                      const std::string& code, int addflag) {
+  constexpr int64_t kPad = 32;  // readable bytes past the text (split_records)
+  if (sep.empty() || sep.size() > 16)
+    fail("mrhip: a device file map splits on a separator of 1 to 16 bytes, " + std::to_string(sep.size()) + " given");
+  const at::Device dev = device();
+  if (!dev.is_cuda()) fail("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  const devfn::Args args = devfn::args_of(dev_args_);
+  Op frame(this, __func__, Op::Deferred());
+  drop_for_map(addflag);
+  frame.enter();
+  KeyValue out(dev);
+  bound(out);
+  const int64_t L = (int64_t)sep.size();
+  at::Tensor host;  // one pinned buffer, grown as needed: every task is done with it before the next read
+  for_chunks(
+      nmap, files, selfflag, recurse, readflag, sep, is_char, delta,
+      [&](int64_t bytes) {
+        if (!host.defined() || host.numel() < bytes + kPad) host = hostarena::pinned_empty({bytes + kPad}, at::kByte);
+        std::memset(host.data_ptr<uint8_t>() + bytes, 0, (size_t)kPad);
+        return reinterpret_cast<char*>(host.data_ptr<uint8_t>());
+      },
+      [&](const FileChunk& c) {
+        const int64_t n = c.s1 - c.s0;
+        if (n <= 0) return;
+        const int64_t nread = std::min<int64_t>(c.got - c.s0, n + L - 1);
+        note_xfer_bytes(true, nread + kPad);
+        const at::Tensor text = to_device(host.narrow(0, c.s0, nread + kPad), dev, /*non_blocking=*/true);
+        // (split_records reads its counts back on this stream: the copy has left the pinned buffer by then)
+        auto [off, nrec] = split_records(text, n, nread, sep, is_char);
+        const int64_t step = functor_chunk(out, nrec);
+        for (int64_t a = 0; a < nrec; a += step) {
+          KV o = devfn::map_records(text, off, nrec, is_char ? 1 : 0, c.ifile, c.st + c.s0, code, dev, a,
+                                    std::min(nrec, a + step), args);
+          if (o.n) out.add_kv(o);
+        }
+      });
+  return finish_map(frame, out, addflag);
 }
 
 uint64_t MapReduce::reduce_device(const std::string& code) {

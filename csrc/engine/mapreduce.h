@@ -134,6 +134,17 @@ class MapReduce {
   // device functors (devfn.h): user HIP device code compiled at run time
   uint64_t map_device(MapReduce& src, const std::string& code, int addflag = 0);
   uint64_t map_device_tasks(int64_t ntask, const std::string& code, int addflag = 0);
+  // map_file_char / map_file_str with a device functor: the files' chunks are
+  // cut into records in HBM (kv.h split_records: sepchar terminates a record,
+  // sepstr starts one; 1 to 16 bytes) and every record goes through mr_map in
+  // place: key = 8 bytes, the file's index in the expanded file list (a long
+  // long), value = the record's bytes, index = the byte offset of the record's
+  // first byte in its file. The output does not depend on nmap or the ranks.
+  uint64_t map_file_char_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
+                                int readflag, char sepchar, int delta, const std::string& code, int addflag = 0);
+  uint64_t map_file_str_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse,
+                               int readflag, const std::string& sepstr, int delta, const std::string& code,
+                               int addflag = 0);
   uint64_t reduce_device(const std::string& code);
   uint64_t compress_device(const std::string& code);
   // stable sort by a device sort functor: mr_sortkey (key -> u64 in the wanted
@@ -292,6 +303,17 @@ class MapReduce {
   uint64_t finish_map(Op& frame, KeyValue& kvb, int addflag, const KV* self = nullptr);
   uint64_t map_chunks(int nmap, const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
                       const std::string& sep, bool is_char, int delta, const MapChunkFn& fn, int addflag);
+  // one task's chunk: `got` bytes of file `ifile` from byte `st` on in buf, the chunk being buf[s0, s1)
+  struct FileChunk {
+    int task, ifile;
+    int64_t st, got, s0, s1;
+    char* buf;
+  };
+  void for_chunks(int nmap, const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
+                  const std::string& sep, bool is_char, int delta, const std::function<char*(int64_t)>& room,
+                  const std::function<void(const FileChunk&)>& fn);
+  uint64_t map_chunks_device(int nmap, const std::vector<std::string>& files, int selfflag, int recurse, int readflag,
+                             const std::string& sep, bool is_char, int delta, const std::string& code, int addflag);
   void run_host_kmv(const KMV& kmv, const std::function<void(char*, int, char*, int, int*)>& fn);
   void histo(double v, const char* heading) const;
   int64_t block_bytes() const;

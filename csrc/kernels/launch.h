@@ -193,6 +193,17 @@ void url_lengths(const uint8_t* text, int64_t n, const int64_t* starts, int64_t 
                  int32_t* keylen, hipStream_t s);
 void url_copy(const uint8_t* text, const int64_t* starts, const int64_t* koff, int64_t nurl,
               uint8_t* kdata, hipStream_t s);
+// record split (engine.cpp split_records): the occurrences of a run-time
+// separator (len 1..16 bytes) at positions p < n with p + len <= nread, all of
+// them, overlapping ones too. Tiles as url_num_tiles(n). sep_count: per-tile
+// counts and *flag (char mode: 1 if byte n - 1 is no occurrence; string mode:
+// 1 if byte 0 is none). sep_emit: out[tile_off[tile] + rank] = p + add, with
+// tile_off the int64 exclusive scan of the counts. text is 16-byte aligned
+// and readable for 32 bytes past nread; what the padding holds does not matter.
+void sep_count(const uint8_t* text, int64_t n, int64_t nread, const uint8_t* sep, int len, bool is_char,
+               uint32_t* tile_counts, uint32_t* flag, hipStream_t s);
+void sep_emit(const uint8_t* text, int64_t n, int64_t nread, const uint8_t* sep, int len, const int64_t* tile_off,
+              int64_t add, int64_t* out, hipStream_t s);
 // whitespace tokenizer (wordfreq): word starts/lengths; keys are word + NUL
 int64_t tok_num_tiles(int64_t n);
 // wordfreq pairs in one pass (text.hip k_tok_count2 / k_tok_emit2): per tile

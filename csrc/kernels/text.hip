@@ -87,6 +87,81 @@ __global__ __launch_bounds__(NT) void k_url_emit(const uint8_t* __restrict__ tex
   }
 }
 
+// Record split (split_records): the separator is a run-time value, 1..16 bytes
+// held as four little-endian words and its length, all kernel arguments (the
+// same for every thread: scalar registers). NW = the words the separator
+// spans, the one thing fixed at compile time: a 9-byte separator costs 3 word
+// compares per position like the built-in above, a 1-byte one a single one.
+// Bit k of the mask: an occurrence at p + k, that is p + k < n (a record may
+// start there) and p + k + L <= nread (all of it lies in the bytes that count:
+// the padding never matches, whatever it holds).
+struct SepWords {
+  uint32_t w[4];  // the separator, bytes past its length zero
+  uint32_t last;  // mask of the bytes it has in its last word
+  int len;
+};
+
+template <int NW>
+__device__ __forceinline__ uint32_t sep_match_mask(const uint8_t* text, int64_t p, int64_t n, int64_t nread,
+                                                   const SepWords sp) {
+  // 16 + 16 bytes from p (p 16-aligned, p < n <= nread, 32 readable bytes past nread)
+  const uint4 a = *reinterpret_cast<const uint4*>(text + p);
+  const uint4 b = *reinterpret_cast<const uint4*>(text + p + 16);
+  const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  // positions k < lim can hold an occurrence (lim <= 0: none)
+  const int64_t l0 = n - p, l1 = nread - sp.len + 1 - p;
+  const int64_t lim = l0 < l1 ? l0 : l1;
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < BYTES_PER_THREAD; ++k) {
+    const int q = k >> 2, r = k & 3;
+    uint32_t diff = 0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+      const uint32_t x = r ? align_bytes(w[q + j + 1], w[q + j], r) : w[q + j];
+      diff |= (x ^ sp.w[j]) & (j == NW - 1 ? sp.last : 0xffffffffu);
+    }
+    m |= (uint32_t)(diff == 0) << k;
+  }
+  return lim >= BYTES_PER_THREAD ? m : lim <= 0 ? 0u : m & ((1u << (int)lim) - 1u);
+}
+
+// flag (one word, the tile counts' last entry): char mode (is_char) 1 when the
+// byte n - 1 is no terminator (an unterminated last record), string mode 1
+// when no occurrence starts at byte 0 (a first record without its separator)
+template <int NW>
+__global__ __launch_bounds__(NT) void k_sep_count(const uint8_t* __restrict__ text, int64_t n, int64_t nread,
+                                                 const SepWords sp, int is_char,
+                                                 uint32_t* __restrict__ tile_counts, uint32_t* __restrict__ flag) {
+  __shared__ uint32_t sh[NT / MRH_WAVE];
+  const int64_t p = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * BYTES_PER_THREAD;
+  const uint32_t m = (p < n) ? sep_match_mask<NW>(text, p, n, nread, sp) : 0u;
+  const int64_t at = is_char ? n - 1 : 0;  // the byte the flag is about
+  if (at >= p && at < p + BYTES_PER_THREAD) *flag = ((m >> (int)(at - p)) & 1u) ^ 1u;
+  uint32_t c = dev::wave_sum((uint32_t)__popc(m));
+  if (dev::lane_id() == 0) sh[dev::wave_id()] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) tile_counts[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// out[tile_off[tile] + rank in the tile] = position + add, for every occurrence
+template <int NW>
+__global__ __launch_bounds__(NT) void k_sep_emit(const uint8_t* __restrict__ text, int64_t n, int64_t nread,
+                                                const SepWords sp, const int64_t* __restrict__ tile_off,
+                                                int64_t add, int64_t* __restrict__ out) {
+  __shared__ uint32_t sh[NT / MRH_WAVE + 1];
+  const int64_t p = (int64_t)blockIdx.x * TILE + (int64_t)threadIdx.x * BYTES_PER_THREAD;
+  uint32_t m = (p < n) ? sep_match_mask<NW>(text, p, n, nread, sp) : 0u;
+  uint32_t total;
+  const uint32_t pos = dev::block_excl_scan<uint32_t, NT>((uint32_t)__popc(m), sh, &total);
+  int64_t o = tile_off[blockIdx.x] + pos;
+  while (m) {
+    const int k = __ffs(m) - 1;
+    m &= m - 1;
+    out[o++] = p + k + add;
+  }
+}
+
 __global__ __launch_bounds__(NT) void k_url_len(const uint8_t* __restrict__ text, int64_t n,
                                                const int64_t* __restrict__ starts, int64_t nurl,
                                                int32_t* __restrict__ keylen) {
@@ -294,6 +369,47 @@ void url_emit_starts(const uint8_t* text, int64_t n, const uint32_t* tile_off, i
   int64_t nt = url_num_tiles(n);
   if (nt <= 0) return;
   hipLaunchKernelGGL(k_url_emit, dim3((unsigned)nt), dim3(NT), 0, s, text, n, tile_off, starts);
+  MRH_CHECK_LAUNCH();
+}
+namespace {
+SepWords sep_words(const uint8_t* sep, int len) {
+  SepWords sp{};
+  uint8_t b[16] = {};
+  for (int i = 0; i < len; ++i) b[i] = sep[i];
+  for (int j = 0; j < 4; ++j)
+    sp.w[j] = (uint32_t)b[4 * j] | (uint32_t)b[4 * j + 1] << 8 | (uint32_t)b[4 * j + 2] << 16 | (uint32_t)b[4 * j + 3] << 24;
+  const int tail = len - 4 * ((len - 1) / 4);  // 1..4 bytes in the last word
+  sp.last = tail == 4 ? 0xffffffffu : (1u << (8 * tail)) - 1u;
+  sp.len = len;
+  return sp;
+}
+}  // namespace
+void sep_count(const uint8_t* text, int64_t n, int64_t nread, const uint8_t* sep, int len, bool is_char,
+               uint32_t* tile_counts, uint32_t* flag, hipStream_t s) {
+  const int64_t nt = url_num_tiles(n);
+  if (nt <= 0 || len < 1 || len > 16) return;
+  const SepWords sp = sep_words(sep, len);
+  const dim3 g((unsigned)nt), b(NT);
+  switch ((len + 3) / 4) {
+    case 1: hipLaunchKernelGGL(k_sep_count<1>, g, b, 0, s, text, n, nread, sp, (int)is_char, tile_counts, flag); break;
+    case 2: hipLaunchKernelGGL(k_sep_count<2>, g, b, 0, s, text, n, nread, sp, (int)is_char, tile_counts, flag); break;
+    case 3: hipLaunchKernelGGL(k_sep_count<3>, g, b, 0, s, text, n, nread, sp, (int)is_char, tile_counts, flag); break;
+    default: hipLaunchKernelGGL(k_sep_count<4>, g, b, 0, s, text, n, nread, sp, (int)is_char, tile_counts, flag);
+  }
+  MRH_CHECK_LAUNCH();
+}
+void sep_emit(const uint8_t* text, int64_t n, int64_t nread, const uint8_t* sep, int len, const int64_t* tile_off,
+              int64_t add, int64_t* out, hipStream_t s) {
+  const int64_t nt = url_num_tiles(n);
+  if (nt <= 0 || len < 1 || len > 16) return;
+  const SepWords sp = sep_words(sep, len);
+  const dim3 g((unsigned)nt), b(NT);
+  switch ((len + 3) / 4) {
+    case 1: hipLaunchKernelGGL(k_sep_emit<1>, g, b, 0, s, text, n, nread, sp, tile_off, add, out); break;
+    case 2: hipLaunchKernelGGL(k_sep_emit<2>, g, b, 0, s, text, n, nread, sp, tile_off, add, out); break;
+    case 3: hipLaunchKernelGGL(k_sep_emit<3>, g, b, 0, s, text, n, nread, sp, tile_off, add, out); break;
+    default: hipLaunchKernelGGL(k_sep_emit<4>, g, b, 0, s, text, n, nread, sp, tile_off, add, out);
+  }
   MRH_CHECK_LAUNCH();
 }
 void url_lengths(const uint8_t* text, int64_t n, const int64_t* starts, int64_t nurl, int32_t* keylen,

@@ -143,6 +143,20 @@ void run_mr_method(Oink& o, int index, const Args& args) {
     if (it == mr_maps().end()) throw Error("Unknown map/mr function " + a[1]);
     std::shared_ptr<MapReduce> src = obj.mrs[j].mr;
     mr.map_mr_batch(*src, it->second, n == 3 ? ival(a[2]) : 0);
+  } else if (cmd == "map/char/device" || cmd == "map/string/device") {
+    // map/char/device nmap files recurse readfile sep delta file [addflag]: map/char with
+    // a device functor (mr_map over the chunks' records), the HIP source read from a file
+    need(7, 8);
+    std::ifstream f(a[6]);
+    if (!f) throw Error("Cannot open device functor file " + a[6]);
+    std::stringstream ss;
+    ss << f.rdbuf();
+    const int add = n == 8 ? ival(a[7]) : 0;
+    if (cmd == "map/char/device")
+      mr.map_file_char_device(ival(a[0]), strings(a[1]), 0, ival(a[2]), ival(a[3]), a[4].empty() ? '\n' : a[4][0],
+                              ival(a[5]), ss.str(), add);
+    else
+      mr.map_file_str_device(ival(a[0]), strings(a[1]), 0, ival(a[2]), ival(a[3]), a[4], ival(a[5]), ss.str(), add);
   } else if (cmd == "map/device" || cmd == "map/mr/device" || cmd == "reduce/device" || cmd == "compress/device" ||
              cmd == "sort_keys/device" || cmd == "sort_values/device" || cmd == "sort_multivalues/device") {
     // device functors (csrc/engine/devfn.h), the HIP source read from a file:

@@ -332,6 +332,31 @@ class MapReduce(metaclass=_Counters):
             return self._with_args(args, lambda: self._m.map_device_tasks(int(src), code, addflag))
         return self._with_args(args, lambda: self._m.map_device(src._m, code, addflag))
 
+    def map_file_char_device(self, nmap, files, selfflag, recurse, readflag, sepchar, delta, code, addflag=0,
+                             args=None):
+        """map_file_char with a device functor: the files are split into
+        ~nmap chunks at `sepchar`, every chunk is cut into records in HBM and
+        every record goes through the same `mr_map` as map_device. `sepchar`
+        terminates a record (the record excludes it; empty records between
+        adjacent terminators are kept; an unterminated last record counts if
+        it is non-empty). key = 8 bytes, `key.as<long long>()` the file's
+        index in the expanded file list; value = the record's bytes, in place
+        in the text; index = the byte offset of the record's first byte in
+        its file. The output does not depend on nmap or the number of ranks."""
+        sep = bytes([sepchar]) if isinstance(sepchar, int) else to_bytes(sepchar)
+        return self._with_args(args, lambda: self._m.map_file_char_device(
+            int(nmap), _files(files), int(selfflag), int(recurse), int(readflag), sep, int(delta), code, int(addflag)))
+
+    def map_file_str_device(self, nmap, files, selfflag, recurse, readflag, sepstr, delta, code, addflag=0, args=None):
+        """map_file_str with a device functor: as map_file_char_device, but
+        `sepstr` (1 to 16 bytes) starts a record: every occurrence, overlapping
+        ones included, begins one that runs to the next occurrence or the end
+        of the file and includes its leading separator; text before the first
+        occurrence is a record of its own if it is non-empty."""
+        return self._with_args(args, lambda: self._m.map_file_str_device(
+            int(nmap), _files(files), int(selfflag), int(recurse), int(readflag), to_bytes(sepstr), int(delta), code,
+            int(addflag)))
+
     def reduce_device(self, code, args=None):
         """reduce with a device functor: every key through `__device__ void
         mr_reduce(mrd::Bytes key, mrd::Values values, mrd::Emit& out[, const
