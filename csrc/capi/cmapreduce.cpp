@@ -255,6 +255,9 @@ void MR_set_device_args(void* p, int nargs, void** ptrs, const uint64_t* nbytes)
 uint64_t MR_scan_device(void* p, const char* code) {
   return guard([&] { return M(p)->scan_device(code); }, (uint64_t)0);
 }
+uint64_t MR_print_device(void* p, const char* file, int fflag, int proc, const char* code) {
+  return guard([&] { return M(p)->print_device(file, fflag, proc, code); }, (uint64_t)0);
+}
 uint64_t MR_sort_keys_device(void* p, const char* code, int bits) {
   return guard([&] { return M(p)->sort_keys_device(code, bits); }, (uint64_t)0);
 }

@@ -108,6 +108,11 @@ void MR_set_device_args(void *MRptr, int nargs, void **device_ptrs, const uint64
 /* read-only functor pass over the KV or KMV: mr_scan (devfn.h) runs once per pair / key and writes
    to the bound buffers (mrd::MutArgs); returns the global pair / key count */
 uint64_t MR_scan_device(void *MRptr, const char *code);
+/* print with a device functor: mr_print (devfn.h) formats every pair / key to text on the GPU
+   (mrd::Text); the text goes where MR_print_file's would (file NULL: the output stream; proc >= 0:
+   that rank alone; fflag 1: file.<rank>; else one file in rank order). The data is left as it is;
+   returns the global bytes written */
+uint64_t MR_print_device(void *MRptr, const char *file, int fflag, int proc, const char *code);
 uint64_t MR_multivalue_blocks(void *MRptr, int *nblock);
 void MR_multivalue_block_select(void *MRptr, int which);
 int MR_multivalue_block(void *MRptr, int iblock, char **ptr_multivalue, int **ptr_valuesizes);

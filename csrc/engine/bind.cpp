@@ -520,6 +520,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("sort_multivalues_device", &MR::sort_multivalues_device, py::arg("code"), py::arg("bits") = 64,
            py::call_guard<py::gil_scoped_release>())
       .def("scan_device", &MR::scan_device, py::arg("code"), py::call_guard<py::gil_scoped_release>())
+      .def("text_device", &MR::text_device, py::arg("code"), py::call_guard<py::gil_scoped_release>())
+      .def("print_device",
+           [](MR& r, py::object file, int fflag, int proc, const std::string& code) {
+             const bool nofile = file.is_none();
+             const std::string path = nofile ? std::string() : file.cast<std::string>();
+             py::gil_scoped_release nogil;
+             return r.print_device(nofile ? nullptr : path.c_str(), fflag, proc, code);
+           },
+           py::arg("file"), py::arg("fflag"), py::arg("proc"), py::arg("code"))
       // None stands for an undefined tensor (rejected with its index, like every other bad entry)
       .def("set_device_args",
            [](MR& r, const std::vector<c10::optional<at::Tensor>>& bufs) {
@@ -1030,6 +1039,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       },
       py::arg("kv"), py::arg("nprocs"), py::arg("code"), py::arg("args") = std::vector<at::Tensor>(),
       py::call_guard<py::gil_scoped_release>());
+  m.def("device_print_check", &devfn::compile_check_print, py::arg("code"), py::arg("kmv"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("device_text_stage_bytes", &devfn::text_stage_bytes);
+  // (staged, direct) workgroup tiles of the print functors' write kernels so far
+  m.def("device_text_tiles", &devfn::text_tiles, py::call_guard<py::gil_scoped_release>());
   m.def("device_functor_compiles", &devfn::compile_count);
   m.def("host_arena_reserve", &hostarena::reserve, py::call_guard<py::gil_scoped_release>());
   m.def("host_arena_stats", [] {

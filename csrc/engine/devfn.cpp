@@ -45,6 +45,11 @@ static_assert(sizeof(Args::Buf) == 16 && sizeof(Args) == kMaxArgs * 16 + 8 && of
 namespace {
 // rows per workgroup tile of the comparator sort (256 threads, 8 rows each)
 constexpr int64_t kCompareTile = 2048;
+// the LDS stage of mrd_text_write. A tile is 256 items; at the 60 - 130 bytes
+// a line of an index or a table takes, 256 lines are 15 - 33 KiB, so 32 KiB
+// stages nearly every such tile and still leaves room for four workgroups
+// (16 waves) on a CU's 160 KiB
+constexpr int64_t kTextStage = 32768;
 
 // a kind's entry points, in the order of its table row
 enum EmitFn { kCount, kWrite, kAccSize, kFoldNChunks, kFoldChunks, kFoldMerge };  // Map, Reduce: the first two
@@ -52,12 +57,13 @@ enum SortKeyFn { kSortKey };
 enum CompareFn { kBlockSort, kMerge };
 enum ScanFn { kScan };
 enum HashFn { kHash };
+enum PrintFn { kTextCount, kTextWrite };
 constexpr int kMaxEntries = 6;
 
 struct KindRow {
   const char* file;                  // the source's name in compiler logs
   const char* define;                // defined in front of the prelude (null: nothing) ...
-  int64_t value;                     // ... as this value; Scan: plus the shape (0 KV, 1 KMV)
+  int64_t value;                     // ... as this value; Scan, Print: plus the shape (0 KV, 1 KMV)
   const char* kernels;               // the device text after the user's code
   const char* entries[kMaxEntries];  // the kernels to resolve
   const char* whose;                 // for the load error
@@ -76,6 +82,8 @@ struct KindRow {
 //   mrd_cmp_merge     (col, const i64* sid, i64 n, const u32* src, u32* dst, i64 W, Args)
 //   mrd_scan          (items, i64 base, i64 n, MutArgs)
 //   mrd_hash          (col, i64 n, int P, int* dest, Args)
+//   mrd_text_count    (items, i64 base, i64 n, i64* cnt, Args)
+//   mrd_text_write    (items, i64 base, i64 n, const i64* pre, u8* out, int stage_ok, u64* tiles, Args)
 // MapText has mrd_count / mrd_write of its own: the same parameters with
 //   records = const u8* text, const i64* off, i64 trim, i64 file, i64 base
 // in the place of items
@@ -91,14 +99,17 @@ const KindRow kKinds[] = {
     {"mrd_scan.hip", "MRD_SCAN_KMV", 0, text::kScanKernel, {"mrd_scan"}, "the scan functor's"},
     {"mrd_hash.hip", nullptr, 0, text::kHashKernel, {"mrd_hash"}, "the partitioner functor's"},
     {"mrd_map_text.hip", nullptr, 0, text::kTextKernels, {"mrd_count", "mrd_write"}, "the device functor's"},
+    {"mrd_print.hip", "MRD_PRINT_KMV", 0, text::kPrintKernels, {"mrd_text_count", "mrd_text_write"},
+     "the print functor's"},
 };
 const KindRow& row_of(Kind kind) { return kKinds[(int)kind]; }
 
-// the full source of a functor; kmv: the KMV shape of mr_scan (Scan only)
+// the full source of a functor; kmv: the KMV shape of mr_scan / mr_print (Scan, Print only)
 std::string source_of(const std::string& code, Kind kind, bool kmv = false) {
   const KindRow& r = row_of(kind);
   std::string src = "#define MRD_ARGS_BYTES " + std::to_string(sizeof(Args)) + "\n";
   if (r.define) src += std::string("#define ") + r.define + " " + std::to_string(r.value + kmv) + "\n";
+  if (kind == Kind::Print) src += "#define MRD_TEXT_STAGE " + std::to_string(kTextStage) + "\n";
   return src + text::kPrelude + code + "\n" + r.kernels;
 }
 
@@ -171,6 +182,15 @@ void need_hash(const std::string& code) {
     throw std::runtime_error(
         "mrhip: a device partitioner functor defines `int mr_hash(mrd::Bytes key)` (MR-MPI's hash callback: the "
         "pair's owner is the result mod the number of ranks); the code has no mr_hash");
+}
+
+// the same for a print source
+void need_print(const std::string& code) {
+  if (code.find("mr_print") == std::string::npos)
+    throw std::runtime_error(
+        "mrhip: a device print functor defines `void mr_print(mrd::Bytes key, mrd::Bytes value, long long index, "
+        "mrd::Text& out)` (KV) or `void mr_print(mrd::Bytes key, mrd::Values values, mrd::Text& out)` (KMV); the code "
+        "has no mr_print");
 }
 
 void need_gpu(at::Device dev) {
@@ -334,6 +354,53 @@ int64_t run_scan(const Items& it, const std::string& code, bool kmv, at::Device 
   launch_items(m.fn[kScan], it.n, at::hip::getCurrentHIPStream(), it, it.first, it.n, bound);
   return it.n;
 }
+
+// the write kernel's tile counters, {staged, direct}: two u64 of device memory
+// per device that ran a print functor, kept for the life of the process
+std::mutex g_tiles_mu;
+std::unordered_map<int, unsigned long long*> g_tiles;
+unsigned long long* tiles_of(int device, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_tiles_mu);
+  auto it = g_tiles.find(device);
+  if (it != g_tiles.end()) return it->second;
+  unsigned long long* p = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&p), 16) != hipSuccess || hipMemsetAsync(p, 0, 16, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError();
+    throw std::runtime_error("mrhip: allocating the print functor's tile counters failed");
+  }
+  return g_tiles.emplace(device, p).first->second;
+}
+int64_t env_i64(const char* name, int64_t dflt) {
+  const char* e = std::getenv(name);
+  return e && *e ? std::atoll(e) : dflt;
+}
+
+// count, scan, write: the text of the items, one contiguous range in item order
+at::Tensor run_print(const Items& it, const std::string& code, bool kmv, at::Device dev, const Args& bound) {
+  need_print(code);
+  if (it.n <= 0) return at::empty({0}, opt(dev, at::kByte));
+  const Module& m = module_for(code, Kind::Print, dev.index(), kmv);
+  hipStream_t s = at::hip::getCurrentHIPStream();
+  at::Tensor cnt = at::empty({it.n}, opt(dev, at::kLong));
+  launch_items(m.fn[kTextCount], it.n, s, it, it.first, it.n, P0<int64_t>(cnt), bound);
+  at::Tensor pre = exclusive_scan(cnt);
+  int64_t bytes = 0;
+  read_small(s, {{P0<int64_t>(pre) + it.n, &bytes, 8}});
+  // MRH_TEXT_LEAD (debug): the text starts that many bytes (mod 16) into its
+  // allocation, as the text of a later piece does inside a larger buffer;
+  // MRH_TEXT_STAGE=0 (measurements): every tile takes the direct route
+  const int64_t lead = env_i64("MRH_TEXT_LEAD", 0) & 15;
+  const int stage_ok = env_i64("MRH_TEXT_STAGE", 1) != 0;
+  at::Tensor out = at::empty({bytes + lead}, opt(dev, at::kByte)).narrow(0, lead, bytes);
+  if (!bytes) return out;
+  const int64_t ntile = (it.n + 255) / 256;
+  const Items& i = it;
+  launch(m.fn[kTextWrite], (unsigned)std::min<int64_t>(ntile, 65536), s, i.k.d, i.k.off, i.k.w, i.v.d, i.v.off, i.v.w,
+         i.seg, i.first, i.n, (const int64_t*)P0<int64_t>(pre), P0<uint8_t>(out), stage_ok,
+         tiles_of(dev.index() < 0 ? 0 : dev.index(), s), bound);
+  return out;
+}
 }  // namespace
 
 std::string full_source(const std::string& code, bool reduce) { return source_of(code, kind_of(code, reduce)); }
@@ -346,6 +413,30 @@ int64_t compile_check_scan(const std::string& code, bool kmv) { return check(cod
 int64_t compile_check_hash(const std::string& code) {
   need_hash(code);
   return check(code, Kind::Hash);
+}
+int64_t compile_check_print(const std::string& code, bool kmv) {
+  need_print(code);
+  return check(code, Kind::Print, kmv);
+}
+int64_t text_stage_bytes() { return kTextStage; }
+std::pair<int64_t, int64_t> text_tiles() {
+  std::lock_guard<std::mutex> lk(g_tiles_mu);
+  std::pair<int64_t, int64_t> t{0, 0};
+  int cur = 0;
+  if (!g_tiles.empty() && hipGetDevice(&cur) != hipSuccess) throw std::runtime_error("mrhip: hipGetDevice failed");
+  for (const auto& e : g_tiles) {
+    unsigned long long c[2] = {0, 0};
+    const bool ok = hipSetDevice(e.first) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                    hipMemcpy(c, e.second, 16, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipSetDevice(cur);
+    if (!ok) {
+      (void)hipGetLastError();
+      throw std::runtime_error("mrhip: reading the print functor's tile counters failed");
+    }
+    t.first += (int64_t)c[0];
+    t.second += (int64_t)c[1];
+  }
+  return t;
 }
 int64_t compile_count() { return g_compiles.load(); }
 int64_t compare_tile() { return kCompareTile; }
@@ -472,6 +563,24 @@ int64_t scan_groups(const KMV& m, const std::string& code, at::Device dev, const
   need_gpu(dev);
   if (m.nkey && !m.seg.is_cuda()) throw std::runtime_error("mrhip: scan_device needs the groups in HBM");
   return run_scan(items_of(m), code, true, dev, bound);
+}
+
+at::Tensor format_pairs(const KV& kv_in, int64_t base, const std::string& code, at::Device dev, const Args& bound) {
+  need_gpu(dev);
+  KV kv = kv_in.device() == dev ? kv_in : kv_to(kv_in, dev);
+  return run_print(items_of(kv, base, kv.n), code, false, dev, bound);
+}
+
+void load_print(const std::string& code, bool kmv, at::Device dev) {
+  need_gpu(dev);
+  need_print(code);
+  module_for(code, Kind::Print, dev.index(), kmv);
+}
+
+at::Tensor format_groups(const KMV& m, const std::string& code, at::Device dev, const Args& bound) {
+  need_gpu(dev);
+  if (m.nkey && !m.seg.is_cuda()) throw std::runtime_error("mrhip: print_device needs the groups in HBM");
+  return run_print(items_of(m), code, true, dev, bound);
 }
 
 }  // namespace devfn

@@ -23,7 +23,7 @@
 // that run one cached module; the module cache key stays (device, kind, scan
 // shape, code), so new contents or new buffers never recompile. Every entry
 // point (mr_map, mr_reduce, mr_init, mr_add, mr_merge, mr_finish, mr_sortkey,
-// mr_compare, mr_hash) MAY take one trailing
+// mr_compare, mr_hash, mr_print) MAY take one trailing
 // `const mrd::Args& args` parameter, each function on its own; args[i] is
 // {p, n bytes} ({nullptr, 0} past the bound count), args[i].as<T>() a
 // `const T*`, args[i].count<T>() the number of T. These functors run more than
@@ -52,8 +52,8 @@ namespace mrh {
 namespace devfn {
 // the functor kinds: mr_map; mr_reduce per key; the fold form (mr_init / mr_add
 // / mr_merge / mr_finish); mr_sortkey; mr_compare; mr_scan; mr_hash; mr_map
-// over the records of a text
-enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan, Hash, MapText };
+// over the records of a text; mr_print
+enum class Kind { Map, Reduce, Fold, SortKey, Compare, Scan, Hash, MapText, Print };
 // the bound buffers as every functor kernel takes them (layout of mrd::Args /
 // mrd::MutArgs in the prelude); slots past n are {nullptr, 0}
 constexpr int kMaxArgs = 8;
@@ -128,6 +128,33 @@ at::Tensor hash_dest(const KV& kv, int P, const std::string& code, at::Device de
 // compile only; the code object size in bytes. Works without a GPU. A source
 // without mr_hash is an error that names it (here and in hash_dest).
 int64_t compile_check_hash(const std::string& code);
+// print functor: the last step of a job, its result as text, formatted on the GPU.
+//   __device__ void mr_print(mrd::Bytes key, mrd::Bytes value, long long index, mrd::Text& out);  // KV
+//   __device__ void mr_print(mrd::Bytes key, mrd::Values values, mrd::Text& out);                   // KMV
+// (either may take a trailing `const mrd::Args& args`) writes an item's text
+// with out.put / chr / str / dec / udec / hex / fixed (mrd::Text in the
+// prelude); it may write nothing. A pure function of its arguments and the
+// bound buffers: it runs twice, count then write, and the write pass never
+// stores past what the count pass measured. One thread per pair / per key
+// (a key with very many values is formatted by one thread, as mr_reduce).
+// Returns the text of kv's pairs (on the GPU; index = base + the pair's
+// position) / of m's keys, in item order: uint8 [bytes] on the device. The
+// write kernel stages a workgroup tile's text in LDS and copies it out in
+// 16-byte lines when the tile's text fits text_stage_bytes(), and writes
+// straight to HBM otherwise (devfn_text.cpp kPrintKernels). n == 0: no launch,
+// an empty tensor. A source without mr_print is an error that names it.
+at::Tensor format_pairs(const KV& kv, int64_t base, const std::string& code, at::Device dev, const Args& args = Args{});
+at::Tensor format_groups(const KMV& m, const std::string& code, at::Device dev, const Args& args = Args{});
+// compiles and loads the functor's module (a no-op once cached): print_device
+// calls it before it opens a file, so a functor that does not compile leaves none behind
+void load_print(const std::string& code, bool kmv, at::Device dev);
+// compile only (kmv: the KMV shape of mr_print); the code object size in bytes. Works without a GPU.
+int64_t compile_check_print(const std::string& code, bool kmv);
+// the LDS stage of the write kernel, in bytes: a tile whose text is longer goes the direct route
+int64_t text_stage_bytes();
+// workgroup tiles the write kernels of this process have run so far, {staged,
+// direct} (device counters, read here: synchronises the devices that ran any)
+std::pair<int64_t, int64_t> text_tiles();
 // hiprtc compilations this process has done so far (checks and module loads alike)
 int64_t compile_count();
 // the full source handed to the compiler (prelude + code + kernels)

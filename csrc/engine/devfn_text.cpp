@@ -90,6 +90,86 @@ struct Emit {
   template <class K>
   __device__ void emit_key(const K& k) { emit(&k, sizeof(K), nullptr, 0); }
 };
+// the text sink of mr_print: counts in the first pass, writes in the second.
+// p is the item's first byte (in HBM, or in the workgroup's LDS stage: a flat
+// pointer either way), room what the count pass measured for the item: a
+// write pass never stores at or past p + room (an impure functor cannot overrun it)
+struct Text {
+  bool write;
+  u8* p;
+  i64 n;     // bytes so far
+  i64 room;  // write pass only
+  __device__ void put(const void* s, i64 m) {
+    if (m <= 0) return;
+    if (write) {
+      const i64 left = room - n, c = m < left ? m : left;
+      for (i64 i = 0; i < c; ++i) p[n + i] = ((const u8*)s)[i];
+    }
+    n += m;
+  }
+  __device__ void put(Bytes b) { put(b.p, b.n); }
+  __device__ void chr(char c) {
+    if (write && n < room) p[n] = (u8)c;
+    ++n;
+  }
+  // a NUL-terminated string (a literal); the NUL is not written
+  __device__ void str(const char* s) {
+    for (; *s; ++s) chr(*s);
+  }
+  __device__ void udec(u64 v) {
+    char b[20];
+    int k = 20;
+    do {
+      b[--k] = (char)('0' + (int)(v % 10));
+      v /= 10;
+    } while (v);
+    put(b + k, 20 - k);
+  }
+  // a minus sign, no plus sign; LLONG_MIN through its unsigned magnitude
+  __device__ void dec(long long v) {
+    if (v < 0) chr('-');
+    udec(v < 0 ? 0ull - (u64)v : (u64)v);
+  }
+  // lower case, no prefix, no leading zeros
+  __device__ void hex(u64 v) {
+    char b[16];
+    int k = 16;
+    do {
+      b[--k] = "0123456789abcdef"[v & 15];
+      v >>= 4;
+    } while (v);
+    put(b + k, 16 - k);
+  }
+  // x with d decimals (d clamped into 0 .. 9): n = |x| * 10^d (one IEEE
+  // multiply by an exact power) rounded half-even to an integer, "-" iff
+  // x < 0 and n != 0, then n / 10^d and, for d > 0, "." and n % 10^d padded
+  // to d digits. nan; inf / -inf; ovf / -ovf when |x| * 10^d >= 2^63.
+  __device__ void fixed(double x, int d) {
+    const double pd[10] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9};
+    const u64 pi[10] = {1ull,      10ull,      100ull,      1000ull,      10000ull,
+                        100000ull, 1000000ull, 10000000ull, 100000000ull, 1000000000ull};
+    d = d < 0 ? 0 : d > 9 ? 9 : d;
+    if (x != x) return str("nan");
+    const bool neg = x < 0;
+    const double a = __builtin_fabs(x);
+    if (a == __builtin_inf()) return str(neg ? "-inf" : "inf");
+    const double m = a * pd[d];
+    if (m >= 9223372036854775808.0) return str(neg ? "-ovf" : "ovf");
+    const u64 r = (u64)__builtin_rint(m);  // round to nearest, ties to even
+    if (neg && r) chr('-');
+    udec(r / pi[d]);
+    if (d) {
+      chr('.');
+      char b[9];
+      u64 f = r % pi[d];
+      for (int k = d - 1; k >= 0; --k) {
+        b[k] = (char)('0' + (int)(f % 10));
+        f /= 10;
+      }
+      put(b, d);
+    }
+  }
+};
 // a device buffer bound to the MapReduce object (set_device_args): p[0 .. n)
 // bytes, read-only to every functor but mr_scan
 struct Arg {
@@ -532,6 +612,103 @@ mrd_hash(const mrd::u8* d, const mrd::i64* off, mrd::i64 w, mrd::i64 n, int P, i
   for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
     const int h = mrd::call_hash(mrd::row(d, off, w, i), args, 0);
     dest[i] = (int)(((mrd::i64)h % P + P) % P);
+  }
+}
+)MRD";
+
+// a print functor, mr_print in its KV (MRD_PRINT_KMV 0) or KMV (1) shape: the
+// text of every item, in item order, as one contiguous byte range.
+//
+//   mrd_text_count  one thread per item (grid-stride): the functor with a
+//                   counting Text, the item's bytes into cnt
+//   mrd_text_write  after the exclusive scan `pre` of cnt: one workgroup per
+//                   tile of TEXT_TILE consecutive items (grid-stride over the
+//                   tiles), one thread per item. The tile owns out[pre[t0],
+//                   pre[t1]). Staged route (the range is at most TEXT_STAGE
+//                   bytes): every thread formats into the LDS stage, then the
+//                   workgroup copies the range out in the output's 16-byte
+//                   lines, whole lines as one 16-byte store each, the partial
+//                   first and last line by bytes. Direct route (a longer
+//                   range): every thread formats straight into HBM.
+//
+// The route follows from pre[t0] and pre[t1] alone: uniform over the workgroup
+// (so are the barriers) and known without a host read. The stage image starts
+// at the 16-byte line of the tile's first output byte: stage[j] is the byte
+// for address line0 + j, the stage is TEXT_STAGE + 16 bytes, and a Text gets
+// {stage + head + (pre[i] - pre[t0]), pre[i + 1] - pre[i]} exactly as it gets
+// {out + pre[i], pre[i + 1] - pre[i]} on the direct route. tiles[0] / tiles[1]
+// count the staged / direct tiles (one atomic per tile).
+const char kPrintKernels[] = R"MRD(
+// ---- mrd print kernels ----
+namespace mrd {
+enum { TEXT_TILE = 256, TEXT_STAGE = MRD_TEXT_STAGE };
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#if MRD_PRINT_KMV
+MRD_SHIM(print, (class T), (Bytes k, Values v, T& t), (k, v, t))
+#else
+MRD_SHIM(print, (class T), (Bytes k, Bytes v, i64 x, T& t), (k, v, x, t))
+#endif
+__device__ inline void print_item(const u8* kd, const i64* koff, i64 kw, const u8* vd, const i64* voff, i64 vw,
+                                  const i64* seg, i64 base, i64 i, Text& t, const Args& g) {
+  const Bytes key = row_or_empty(kd, koff, kw, i);
+#if MRD_PRINT_KMV
+  Values vals{vd, voff, vw, seg[i + 1] - seg[i]};
+  if (voff) vals.off = voff + seg[i];
+  else vals.d = vd + seg[i] * vw;
+  call_print(key, vals, t, g, 0);
+#else
+  call_print(key, row_or_empty(vd, voff, vw, i), base + i, t, g, 0);
+#endif
+}
+}  // namespace mrd
+extern "C" __global__ __launch_bounds__(256) void
+mrd_text_count(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff,
+               mrd::i64 vw, const mrd::i64* seg, mrd::i64 base, mrd::i64 n, mrd::i64* cnt, mrd::Args args) {
+  for (mrd::i64 i = (mrd::i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (mrd::i64)gridDim.x * 256) {
+    mrd::Text t{false, nullptr, 0, 0};
+    mrd::print_item(kd, koff, kw, vd, voff, vw, seg, base, i, t, args);
+    cnt[i] = t.n;
+  }
+}
+extern "C" __global__ __launch_bounds__(256) void
+mrd_text_write(const mrd::u8* kd, const mrd::i64* koff, mrd::i64 kw, const mrd::u8* vd, const mrd::i64* voff,
+               mrd::i64 vw, const mrd::i64* seg, mrd::i64 base, mrd::i64 n, const mrd::i64* pre, mrd::u8* out,
+               int stage_ok, unsigned long long* tiles, mrd::Args args) {
+  using namespace mrd;
+  __shared__ __attribute__((aligned(16))) u8 stage[TEXT_STAGE + 16];
+  const i64 ntile = (n + TEXT_TILE - 1) / TEXT_TILE;
+  for (i64 tile = blockIdx.x; tile < ntile; tile += gridDim.x) {  // uniform over the workgroup
+    const i64 t0 = tile * TEXT_TILE, t1 = t0 + TEXT_TILE < n ? t0 + TEXT_TILE : n;
+    const i64 o0 = pre[t0], len = pre[t1] - o0;
+    const bool staged = stage_ok && len <= TEXT_STAGE;
+    if (threadIdx.x == 0) atomicAdd(tiles + (staged ? 0 : 1), 1ull);
+    if (len <= 0) continue;
+    const i64 i = t0 + threadIdx.x;
+    const i64 a = i < t1 ? pre[i] : 0, room = i < t1 ? pre[i + 1] - a : 0;
+    if (!staged) {
+      if (room > 0) {
+        Text t{true, out + a, 0, room};
+        print_item(kd, koff, kw, vd, voff, vw, seg, base, i, t, args);
+      }
+      continue;
+    }
+    const int head = (int)((unsigned long long)(out + o0) & 15);
+    if (room > 0) {  // a - o0 + room <= len <= TEXT_STAGE: inside the stage
+      Text t{true, stage + head + (a - o0), 0, room};
+      print_item(kd, koff, kw, vd, voff, vw, seg, base, i, t, args);
+    }
+    __syncthreads();
+    u8* line0 = out + o0 - head;  // 16-byte aligned; stage[j] belongs at line0[j]
+    const int end = head + (int)len;
+    for (int lo = (int)threadIdx.x * 16; lo < end; lo += 256 * 16) {
+      if (lo >= head && lo + 16 <= end) {
+        *reinterpret_cast<u32x4*>(line0 + lo) = *reinterpret_cast<const u32x4*>(stage + lo);
+      } else {
+        const int b0 = lo > head ? lo : head, b1 = lo + 16 < end ? lo + 16 : end;
+        for (int b = b0; b < b1; ++b) line0[b] = stage[b];
+      }
+    }
+    __syncthreads();  // the stage is free for the next tile
   }
 }
 )MRD";

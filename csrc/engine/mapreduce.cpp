@@ -1772,16 +1772,22 @@ void MapReduce::print(const char* file, int fflag, int proc, int nstride, int kf
               fmt_item(k.at(i), k.len(i), kflag) + ", values " + vs + "\n";
     }
   }
+  write_text(file, fflag, proc, [&](const TextSink& sink) { sink(text.data(), text.size()); });
+}
+
+void MapReduce::write_text(const char* file, int fflag, int proc, const std::function<void(const TextSink&)>& body) {
+  const int me = comm_->rank();
   auto emit = [&](const char* path, const char* mode) {
     if (!path) {
-      out(text);
+      body([](const char* b, size_t n) { out(std::string(b, n)); });
       return;
     }
-    std::FILE* f = std::fopen(path, mode);
+    std::unique_ptr<std::FILE, int (*)(std::FILE*)> f(std::fopen(path, mode), &std::fclose);
     if (!f) fail(std::string("Could not open print file ") + path);
-    std::fwrite(text.data(), 1, text.size(), f);
-    std::fclose(f);
-    wsize += (int64_t)text.size();
+    body([&](const char* b, size_t n) {
+      std::fwrite(b, 1, n, f.get());
+      wsize += (int64_t)n;
+    });
   };
   if (proc >= 0) {
     if (proc == me) emit(file, "w");
@@ -1799,6 +1805,84 @@ void MapReduce::print(const char* file, int fflag, int proc, int nstride, int kf
     if (r == me && !(file && me == 0)) emit(file, "a");
   }
   comm_->barrier();
+}
+
+// print with a device functor: pairs / groups in HBM are formatted by one
+// launch pair; host-resident data (past the HBM budget) goes through HBM in
+// budget-sized pieces as for scan_device, a pair's index its index on this
+// rank. The data stays where and as it is.
+void MapReduce::for_each_text(const std::string& code, const std::function<void(const at::Tensor&)>& fn) {
+  const at::Device dev = device();
+  const devfn::Args bound = devfn::args_of(dev_args_);
+  if (kv) {
+    if (kv->n && !kv->device().is_cuda()) {
+      OocStats os;
+      ooc_for_each_kv_piece(*kv, ooc_env(), dev,
+                            [&](const KV& piece, int64_t first) { fn(devfn::format_pairs(piece, first, code, dev, bound)); },
+                            &os);
+      note_ooc("Print", os);
+    } else {
+      fn(devfn::format_pairs(*kv, 0, code, dev, bound));
+    }
+    return;
+  }
+  need_kmv("print");
+  OocStats os;
+  bool pieces = false;
+  for (const KMV& m : kmv_parts()) {
+    if (!m.nkey) continue;
+    if (!m.seg.is_cuda() || needs_ooc(m.nbytes(), budget(), 2.0)) {
+      pieces = true;
+      ooc_for_each_kmv_piece(m, ooc_env(), dev,
+                             [&](const KMV& piece) { fn(devfn::format_groups(piece, code, dev, bound)); }, &os);
+    } else {
+      fn(devfn::format_groups(m, code, dev, bound));
+    }
+  }
+  if (pieces) note_ooc("Print", os);
+}
+
+at::Tensor MapReduce::text_device(const std::string& code) {
+  Op frame(this, __func__, Op::Deferred());
+  const at::Device dev = device();
+  if (!dev.is_cuda()) fail("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  frame.enter(true, false, true);
+  if (!kv) need_kmv("print");
+  devfn::load_print(code, !kv, dev);
+  std::vector<at::Tensor> texts;
+  for_each_text(code, [&](const at::Tensor& t) {
+    if (t.numel()) texts.push_back(t);
+  });
+  if (kv) frame.kv_done("Text");
+  else frame.kmv_done("Text");
+  if (texts.empty()) return at::empty({0}, at::TensorOptions().device(dev).dtype(at::kByte));
+  return texts.size() == 1 ? texts[0] : at::cat(texts);
+}
+
+uint64_t MapReduce::print_device(const char* file, int fflag, int proc, const std::string& code) {
+  Op frame(this, __func__, Op::Deferred());
+  if (!device().is_cuda()) fail("mrhip: device functors run on a GPU MapReduce (device cuda)");
+  frame.enter(true, false, true);
+  if (!kv) need_kmv("print");
+  devfn::load_print(code, !kv, device());
+  // a piece's text reaches the sink through pinned host memory, at most kHostText bytes at a time
+  constexpr int64_t kHostText = int64_t(64) << 20;
+  at::Tensor host;
+  int64_t written = 0;
+  write_text(file, fflag, proc, [&](const TextSink& sink) {
+    for_each_text(code, [&](const at::Tensor& t) {
+      for (int64_t a = 0; a < t.numel(); a += kHostText) {
+        const int64_t n = std::min<int64_t>(kHostText, t.numel() - a);
+        if (!host.defined() || host.numel() < n) host = hostarena::pinned_empty({n}, at::kByte);
+        host.narrow(0, 0, n).copy_(t.narrow(0, a, n));  // not non_blocking: complete on return
+        sink(reinterpret_cast<const char*>(host.data_ptr()), (size_t)n);
+        written += n;
+      }
+    });
+  });
+  if (kv) frame.kv_done("Print");
+  else frame.kmv_done("Print");
+  return count(written);
 }
 
 // ====================================================================== stats

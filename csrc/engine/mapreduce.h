@@ -214,6 +214,18 @@ class MapReduce {
   // print (reference :1671-1761): kflag/vflag 0 none,1 int,2 uint64,3 float,4 double,5 str,6 strn,7 raw bytes
   void print(int proc, int nstride, int kflag, int vflag);
   void print(const char* file, int fflag, int proc, int nstride, int kflag, int vflag);
+  // print with a device functor (devfn.h, mr_print in its KV or KMV shape):
+  // the pairs / keys of this rank formatted to text on the GPU, in item order;
+  // the data is left as it is. Data past the HBM budget is formatted piece by
+  // piece, the pieces' texts in order; index is the pair's index on this rank.
+  // text_device: this rank's text, uint8 [bytes] in HBM.
+  // print_device: the text written out under print's file and rank rules (file
+  // null: the output stream; proc >= 0: that rank alone; fflag 1: file.<rank>;
+  // else one file in rank order); every piece goes through pinned host memory.
+  // Returns the global bytes written. No nstride: a functor skips an item by
+  // writing nothing.
+  at::Tensor text_device(const std::string& code);
+  uint64_t print_device(const char* file, int fflag, int proc, const std::string& code);
 
   uint64_t kv_stats(int level);
   uint64_t kmv_stats(int level);
@@ -294,6 +306,14 @@ class MapReduce {
   void emit_kv(const std::vector<KMV>& src, const ReduceFn& fn);
   void need_kv(const char* what) const;
   void need_kmv(const char* what) const;
+  // the tail of print and print_device: which rank writes where and when
+  // (proc, fflag, the token ring). `body` runs on a rank when it is that
+  // rank's turn and hands its text, in one or more pieces, to the sink it
+  // gets; file bytes are added to wsize
+  using TextSink = std::function<void(const char* bytes, size_t n)>;
+  void write_text(const char* file, int fflag, int proc, const std::function<void(const TextSink&)>& body);
+  // every piece of this rank's device-functor text (print_device / text_device), in order
+  void for_each_text(const std::string& code, const std::function<void(const at::Tensor&)>& fn);
   uint64_t sort_column(bool by_value, int flag);
   uint64_t sort_column(bool by_value, const CompareFn& fn);
   uint64_t sort_column_device(bool by_value, const std::string& code, int bits);

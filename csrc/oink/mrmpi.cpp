@@ -198,6 +198,14 @@ void run_mr_method(Oink& o, int index, const Args& args) {
     std::stringstream ss;
     ss << f.rdbuf();
     mr.scan_device(ss.str());
+  } else if (cmd == "print/device") {
+    // print/device file fflag proc codefile: mr_print formats every pair / key on the GPU; file NULL = the screen
+    need(4, 4);
+    std::ifstream f(a[3]);
+    if (!f) throw Error("Cannot open device functor file " + a[3]);
+    std::stringstream ss;
+    ss << f.rdbuf();
+    mr.print_device(a[0] == "NULL" ? nullptr : a[0].c_str(), ival(a[1]), ival(a[2]), ss.str());
   } else if (cmd == "device_args") {
     // device_args v1 v2 ...: the values as one float64 device buffer, argument
     // 0 of every later */device command (a loop changes a parameter without

@@ -399,6 +399,26 @@ class MapReduce(metaclass=_Counters):
         data is left as it is; returns the global pair / key count."""
         return self._with_args(args, lambda: self._m.scan_device(code))
 
+    def text_device(self, code, args=None):
+        """this rank's pairs / keys formatted to text on the GPU by a device
+        print functor: `__device__ void mr_print(mrd::Bytes key, mrd::Bytes
+        value, long long index, mrd::Text& out)` over the KV or
+        `mr_print(mrd::Bytes key, mrd::Values values, mrd::Text& out)` over
+        the KMV (either may take a trailing `const mrd::Args& args`). `out`
+        has put / chr / str / dec / udec / hex / fixed; an item may write
+        nothing. Returns the text in item order, a torch.uint8 tensor in
+        HBM; the data is left as it is."""
+        return self._with_args(args, lambda: self._m.text_device(code))
+
+    def print_device(self, file, fflag, proc, code, args=None):
+        """text_device written out under print's rules: file None = the
+        output stream, proc >= 0 = that rank alone, fflag 1 = `file.<rank>`,
+        else one file in rank order. Returns the global bytes written."""
+        if file is None:
+            _route_screen()
+        return self._with_args(args, lambda: self._m.print_device(None if file is None else str(file), int(fflag),
+                                                                  int(proc), code))
+
     def scan_kv(self, fn, ptr=None):
         """Read-only fn(key, value[, ptr]) over the KV (reference :1933-1976)."""
         return self._m.scan_kv(_bind(fn, 2, ptr))
